@@ -9,6 +9,12 @@ N>1: one shard of 1 Mi nodes per GPU (weak scaling), the SAME two models, kRando
 are packed per destination shard behind the tick's launch and travel as one equal-split RCCL all-to-all per round (the
 bijection's all-to-all is issued chunk-wise and overlapped with compute).  Prints ONE JSON line on rank 0.
 
+A plain run measures the headline alone: set-up, pre-roll, warm-up, the `--steps` timed ticks of the headline model and
+its roofline, then the line.  Everything else is measured with `--full`: the bijection next to it (`fanout_models`), the
+long window, rounds-to-99 %, the N > 1 exchange diagnosis, the second load, and the CPU baseline with its parity digests.
+`--dump-outputs DIR` writes the state the headline cluster holds right after its last timed tick (timed_outputs) as
+DIR/<name>.npy; the inputs depend on the arguments alone, so two builds compare output for output.
+
 `python bench.py --gpus N` without a launcher (WORLD_SIZE unset) starts its N ranks itself (one process per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set for them, rendezvous on 127.0.0.1) and supervises them: a rank that dies
 or a run that stops making progress is torn down, retried once with `--chunks 1`, and reported as a JSON line with an
@@ -28,6 +34,8 @@ import subprocess
 import sys
 import threading
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -128,7 +136,9 @@ def cpu_baseline(args, model, parity_ticks, timed=True, seconds_budget=300.0):
     and the tick right after its last timed one) for the parity block.  With `timed`, the ticks of the timed region — at most
     32 of them — are timed on all cores, and 8 more on one thread behind the last parity tick.  When the host cannot hold the
     configuration (it needs ~64 KiB of address space per node, a fraction of it resident) it falls back to a smaller cluster,
-    says so, and the parity block is void."""
+    says so, and the parity block is void.  The oracle gets `seconds_budget` of CPU time: a parity tick it cannot reach in it
+    (a long timed region: the GPU covers in seconds what takes the oracle minutes) is not rolled to — its digest is None and
+    the third value says why — and without the first one there is no timed figure either (None)."""
     from serf_amd import _ffi
 
     lib = _ffi.SimLib(os.path.join(ROOT, "oracle", "liboracle.so"), prefix="osim_")  # test infrastructure: the checker, timed
@@ -152,18 +162,27 @@ def cpu_baseline(args, model, parity_ticks, timed=True, seconds_budget=300.0):
     first, last = parity_ticks[0], parity_ticks[-1]
 
     def roll(to):
+        """True once the oracle stands at tick `to`; False when the budget ran out on the way"""
         nonlocal rolled
         while rolled < to:  # untimed, like the GPU run's pre-roll + warm-up — never shortened
+            if time.perf_counter() - t0 > seconds_budget:
+                return False
             k = min(5, to - rolled)
             sim.step(k)
             rolled += k
-            if time.perf_counter() - t0 > seconds_budget:
-                raise SystemExit(f"bench.py: the CPU oracle needed more than {seconds_budget:.0f} s for {rolled} of {last} ticks "
-                                 "on this host — cpu_baseline would not be timing the GPU's ticks; rerun with --no-cpu-baseline or a smaller --preroll")
+        return True
 
-    roll(first)
+    def out_of_budget(t):
+        return (f"the CPU oracle would need more than its {seconds_budget:.0f} s to reach tick {t} on this host (it stood at tick "
+                f"{rolled} after {time.perf_counter() - t0:.0f} s): not rolled, not compared")
+
+    if not roll(first):
+        sim.close()
+        return None, {t: None for t in parity_ticks}, out_of_budget(first)
     t_roll = time.perf_counter() - t0
+    per_tick = t_roll / max(1, first)
     digests = {first: sim.digest() if n == args.nodes_per_gpu else None}
+    why = None if n == args.nodes_per_gpu else f"the host could not hold the configuration{note}: the oracle ran a smaller cluster"
     done, dt = 0, 0.0
     if timed:  # the first ticks of the GPU's timed region, on all cores
         ticks_all = min(32, last - first)
@@ -175,7 +194,11 @@ def cpu_baseline(args, model, parity_ticks, timed=True, seconds_budget=300.0):
         dt = time.perf_counter() - t1
         rolled += done
     for t in parity_ticks[1:]:
-        roll(t)
+        # (the rest of the way at the pre-roll's pace, before it is started: a roll that cannot end in the budget is not begun)
+        if time.perf_counter() - t0 + (t - rolled) * per_tick > seconds_budget or not roll(t):
+            digests[t] = None
+            why = why or out_of_budget(t)
+            continue
         digests[t] = sim.digest() if n == args.nodes_per_gpu else None
     res = None
     if timed:
@@ -206,10 +229,10 @@ def cpu_baseline(args, model, parity_ticks, timed=True, seconds_budget=300.0):
                "sample_short": f"{n} nodes, same config+schedule; ticks {first}..{first + done - 1} on {cores} threads (cgroup quota; host shows {host_cores} CPUs: curve in detail), {done1} ticks on 1",
                "sample": f"same configuration, fan-out model ({model}) and schedule as the GPU run{note}: {n} nodes, view_slots {args.view_slots}, "
                          f"rings {args.ring}, fan-out {args.fanout}; {first} untimed pre-roll ticks ({t_roll:.1f} s), then ticks {first}..{first + done - 1} "
-                         f"timed on {cores} threads (OpenMP over nodes), on to tick {last} for the second parity digest, and {done1} more on one "
+                         f"timed on {cores} threads (OpenMP over nodes), on to tick {rolled} for the second parity digest, and {done1} more on one "
                          f"thread; model_bound_drops {drops}"}
     sim.close()
-    return res, digests
+    return res, digests, why
 
 
 def second_load(args, lib, dev, torch):
@@ -289,11 +312,13 @@ def second_load(args, lib, dev, torch):
                    f"{a2.ring_overflow} overflow rows; frac = B_tick(f, P = 16) x nodes / tick-kernel time (the deep kernel's time is in ms_per_step)"}
     if args.second_parity:
         progress_ticks = [a2.preroll + a2.warmup, a2.preroll + a2.warmup + a2.steps]
-        _, dig = cpu_baseline(a2, model, progress_ticks, timed=False, seconds_budget=3600.0)
-        ok = [tuple(dig[t]) == tuple(d) for t, d in zip(progress_ticks, (d0, d1))]
-        out["digest_match"] = all(ok)
+        _, dig, why = cpu_baseline(a2, model, progress_ticks, timed=False, seconds_budget=3600.0)
+        ok = [None if dig[t] is None else tuple(dig[t]) == tuple(d) for t, d in zip(progress_ticks, (d0, d1))]
+        out["digest_match"] = None if None in ok else all(ok)
         out["parity"] = {"ticks": progress_ticks, "digest_match_per_tick": ok, "gpu": [[f"{x:016x}" for x in d] for d in (d0, d1)],
-                         "oracle": [[f"{x:016x}" for x in dig[t]] for t in progress_ticks]}
+                         "oracle": [None if dig[t] is None else [f"{x:016x}" for x in dig[t]] for t in progress_ticks]}
+        if why:
+            out["parity"]["why"] = why
     sim.close()
     return out
 
@@ -343,12 +368,78 @@ def parse_args(argv=None):
     ap.add_argument("--watchdog", type=float, default=120.0,
                     help="N > 1: seconds without progress after which a rank gives up (a JSON line with \"error\" on rank 0, exit code 3)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="self-launched N > 1 run: seconds the supervisor waits for its ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline: the other fan-out model (fanout_models), the long window, "
+                         "rounds-to-99 %%, the N > 1 exchange diagnosis, the second load and the CPU baseline with its parity digests")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline cluster holds right after its last timed step to DIR/<name>.npy (float64; "
+                         "a fixed, seeded sample of nodes; see timed_outputs)")
     a = ap.parse_args(argv)
     if a.random_fanout:
         a.fanout_model = "krandomnodes"
     if a.force_sharded and a.fanout_model == "both":
         a.fanout_model = "bijection"   # (the one-rank rehearsal: one model per run; --fanout-model krandomnodes: the packed slabs)
     return a
+
+
+OUT_SAMPLE_ROWS, OUT_SAMPLE_QUEUES, OUT_OBSERVERS, OUT_SEED = 65536, 8192, 4, 20260401
+
+
+def _u64_halves(a):
+    """u64 values as two exact float64 columns (high 32 bits, low 32 bits), on a new last axis"""
+    a = np.asarray(a, dtype=np.uint64)
+    return np.stack([(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+
+def timed_outputs(raw, sharded):
+    """What a caller of the timed path holds after its last step, as float64 arrays (~42 MB at 1 Mi nodes): every u64 is
+    split into exact high / low 32-bit halves.  Node samples are drawn with a fixed seed from the local node count, so two
+    runs with the same arguments compare array for array.
+      digest         [8, 2]             sim_state_digest (all state arrays)
+      rows           [S, 36]            the node rows of a sample of nodes (ROW_DTYPE fields in order)
+      queue          [S', Q, 4]         the broadcast queues of a smaller sample: key, meta, val high, val low
+      members        [K, S, 3]          (one GPU) the member table of K observers over the row sample: status, ltime high / low
+      cluster_stats  [15]               sim_cluster_stats_get and the tick"""
+    from serf_amd import _ffi
+
+    out = {"digest": _u64_halves(raw.digest())}
+    rows = raw.dump(_ffi.ARR_ROWS)
+    n = len(rows)
+    rng = np.random.default_rng(OUT_SEED)
+    pick = np.sort(rng.choice(n, size=min(n, OUT_SAMPLE_ROWS), replace=False))
+    cols = []
+    for name in _ffi.ROW_DTYPE.names:
+        v = rows[name][pick]
+        if v.dtype == np.uint64:
+            cols.append(_u64_halves(v))
+        else:
+            cols.append(v.reshape(len(pick), -1).astype(np.float64))
+    out["rows"] = np.concatenate(cols, axis=1)
+    del rows
+    qpick = np.sort(rng.choice(n, size=min(n, OUT_SAMPLE_QUEUES), replace=False))
+    q = raw.dump(_ffi.ARR_QUEUE).reshape(n, _ffi.Q)[qpick]
+    out["queue"] = np.concatenate([q["key"][..., None].astype(np.float64), q["meta"][..., None].astype(np.float64),
+                                   _u64_halves(q["val"])], axis=-1)
+    del q
+    if not sharded:
+        observers = np.sort(rng.choice(n, size=min(n, OUT_OBSERVERS), replace=False))
+        mem = []
+        for ob in observers:
+            st, lt = raw.members(int(ob))
+            mem.append(np.concatenate([st[pick][:, None].astype(np.float64), _u64_halves(lt[pick])], axis=1))
+        out["members"] = np.stack(mem)
+    cs = raw.cluster_stats()
+    out["cluster_stats"] = np.array([cs["up"], *cs["queued"], cs["overflow"], cs["inbox_records"], cs["failed"], cs["left"],
+                                     cs["max_queue"], cs["ops_dropped"], cs["slots_in_use"], cs["slots_recycled"],
+                                     cs["events_lost"], raw.tick], dtype=np.float64)
+    return out
+
+
+def write_outputs(outputs, d, rank, world):
+    """DIR/<name>.npy (rank r of a run over N > 1 GPUs: DIR/<name>_rank<r>.npy, its own shard)"""
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 _OUT = None  # the process's REAL stdout once run() has claimed it (see claim_stdout)
@@ -411,6 +502,8 @@ def compact(out):
     if out.get("parity"):
         line["parity"] = {"digest_match": out["parity"].get("digest_match"), "ticks": out["parity"].get("ticks"),
                           "models": [k for k, v in out["parity"].items() if isinstance(v, dict)]}
+        if out["parity"].get("not_compared"):
+            line["parity"]["not_compared"] = out["parity"]["not_compared"]
     line["rounds_to_99"] = rounds(out.get("rounds_to_99"))
     fm = {}
     for mo, d in out.get("fanout_models", {}).items():
@@ -529,8 +622,8 @@ def run(args, lib=None, dev=None, backend="nccl"):
     n_total = args.nodes_per_gpu * world
     if lib is None:
         lib = serf_amd.load()
-    if args.fanout_model == "both":   # at every N: the reference's model first — the headline, ONE series from 1 to 8 GPUs —, the bijection next to it
-        models = ["krandomnodes", "bijection"]
+    if args.fanout_model == "both":   # at every N: the reference's model first — the headline, ONE series from 1 to 8 GPUs —, the bijection next to it (--full)
+        models = ["krandomnodes", "bijection"] if args.full else ["krandomnodes"]
     else:
         models = [args.fanout_model]
     sharded = world > 1 or args.force_sharded
@@ -648,7 +741,7 @@ def run(args, lib=None, dev=None, backend="nccl"):
         # parity block: the state the timed region starts from and the state it ends in, digested (all 8 arrays); rank 0's
         # cpu_baseline() rolls the oracle through the same schedule to the same ticks and compares
         m["parity_ticks"] = [args.preroll + args.warmup, args.preroll + args.warmup + args.steps]
-        want_parity = world == 1 and not args.no_cpu_baseline and (model == models[0] or args.parity_all)
+        want_parity = world == 1 and args.full and not args.no_cpu_baseline and (model == models[0] or args.parity_all)
         m["digests"] = {}
         if want_parity:
             m["digests"][m["parity_ticks"][0]] = raw.digest()
@@ -657,12 +750,20 @@ def run(args, lib=None, dev=None, backend="nccl"):
         if want_parity:
             m["digests"][m["parity_ticks"][1]] = raw.digest()
         m["load1"] = load_now()
-        # second window: 300 further ticks timed the same way — push-pull batch (every 300) and recycling passes (every 75) inside
-        m["long"] = timed(long_window(args), 4) if long_window(args) else None
-        # N > 1 diagnosis, outside the timed region: the same ticks with every all-to-all bracketed by events and run
+        if args.dump_outputs and model == models[0]:   # (after load_now: a sharded round's exchanges have landed)
+            write_outputs(timed_outputs(raw, sharded), args.dump_outputs, rank, world)
+            progress("dump outputs")
+        # (--full) second window: 300 further ticks timed the same way — push-pull batch (every 300) and recycling passes (every 75) inside
+        m["long"] = timed(long_window(args), 4) if long_window(args) and args.full else None
+        # (--full) N > 1 diagnosis, outside the timed region: the same ticks with every all-to-all bracketed by events and run
         # synchronously (no overlap) — what one round's exchange costs on its own, next to the kernel
-        m["exchange_ms"], diag_ticks = None, 20
+        m["exchange_ms"], m["serial_ms"], m["diag_ticks"] = None, None, 0
         if sharded:
+            m["chunks"] = sim.chunks
+            m["exchange_bytes"] = raw.exchange_bytes()
+            m["collectives"] = sim.collective_library()
+        if sharded and args.full:
+            diag_ticks = 20
             barrier()
             sim.time_exchange(True)
             td0 = time.perf_counter()
@@ -671,13 +772,10 @@ def run(args, lib=None, dev=None, backend="nccl"):
             m["serial_ms"] = (time.perf_counter() - td0) * 1e3 / diag_ticks
             m["exchange_ms"] = sim.time_exchange(False) / diag_ticks
             m["diag_ticks"] = diag_ticks
-            m["chunks"] = sim.chunks
-            m["exchange_bytes"] = raw.exchange_bytes()
-            m["collectives"] = sim.collective_library()
         # ---- second half of the metric: rounds to 99 % convergence of the workload's OWN user events (no extra load),
         # every one issued in a fixed window of ticks, all outstanding ones polled with one launch per tick
         rounds, conv_first, conv_last = [], None, None
-        if not args.no_convergence:
+        if args.full and not args.no_convergence:
             c0 = conv_start_tick(args)
             step(c0 - raw.tick)
             evs = [(t, node, a) for (t, op, node, a, b) in ops if op == _ffi.OP_USER_EVENT and c0 <= t < c0 + CONV_WINDOW][:CONV_RUMOURS]
@@ -800,7 +898,8 @@ def run(args, lib=None, dev=None, backend="nccl"):
                            "what": f"the timed region runs each tick as {m['chunks']} chunk launches with the all-to-all of chunk c in flight "
                                    "while chunk c + 1 computes (overlapped_ms_per_step = ms_per_step); exchange_ms and serial_ms_per_step come "
                                    f"from {m['diag_ticks']} further ticks with the collectives run one after the other between events (rank 0): "
-                                   "exchange_ms = all-to-alls of one round, serial_ms_per_step = that round without overlap"}
+                                   "exchange_ms = all-to-alls of one round, serial_ms_per_step = that round without overlap"
+                                   + ("" if m["diag_ticks"] else " (measured with --full only: null here)")}
 
     def summary_of(m):
         t, lw = m["timed"], m["long"]
@@ -853,7 +952,7 @@ def run(args, lib=None, dev=None, backend="nccl"):
                                    f"{args.push_pull_interval} ticks (x log2 scaling), reaper and queue checker on — BASELINE configs[2]; "
                                    f"{args.preroll} untimed pre-roll ticks under the same load before the warm-up (steady state); the timed region is the "
                                    f"{args.steps} ticks the driver asks for (not SURVEY §8d's 1 000)"
-                                   + (f", the {long_window(args)} ticks behind it are measured as well (long_window)" if long_window(args) else ""),
+                                   + (f", the {long_window(args)} ticks behind it are measured as well (long_window)" if head["long"] else ""),
                        "workload_short": f"BASELINE configs[2]: {n_total} nodes ({args.nodes_per_gpu}/GPU), fan-out {args.fanout}, {models[0]}, {args.rate} API ops/tick, "
                                          f"{args.pkt_records} records/packet, view_slots {args.view_slots}, rings {args.ring}, probe {args.probe_interval}, push-pull {args.push_pull_interval}, "
                                          f"{args.preroll} pre-roll ticks",
@@ -890,33 +989,39 @@ def run(args, lib=None, dev=None, backend="nccl"):
             out["exchange"] = exchange_of(head)
             out["distributed"] = {"backend": dist.get_backend() if world > 1 else None, "world_size": world,
                                   "collective_library": head["collectives"]}
-        if world == 1 and on_gpu and not args.no_second_load and args.pkt_records == 4 and not sharded:
+        if world == 1 and on_gpu and args.full and not args.no_second_load and args.pkt_records == 4 and not sharded:
             progress("second load")
             out["second_load"] = second_load(args, lib, dev, torch)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["parity"] = {}
             for i, mo in enumerate(models):
                 if i > 0 and not args.parity_all:   # one oracle roll per run by default: the lease is for the GPU
                     continue
                 progress(f"cpu_baseline ({mo})")
                 m = res[mo]
-                cb, cpu_dig = cpu_baseline(args, mo, m["parity_ticks"], timed=(i == 0))
-                if i == 0:
+                cb, cpu_dig, why = cpu_baseline(args, mo, m["parity_ticks"], timed=(i == 0))
+                if i == 0 and cb is not None:
                     out["cpu_baseline"] = cb
                 pt = m["parity_ticks"]
-                if any(cpu_dig[tk] is None for tk in pt):
-                    out["parity"][mo] = {"ticks": pt, "digest_match": None, "why": "the host could not hold the configuration: oracle ran a smaller cluster"}
+                cmp = [tk for tk in pt if cpu_dig[tk] is not None]   # the ticks the oracle reached (all of them, but on a long timed region)
+                if not cmp:
+                    out["parity"][mo] = {"ticks": pt, "digest_match": None, "why": why}
                 else:
-                    ok = [tuple(cpu_dig[tk]) == tuple(m["digests"][tk]) for tk in pt]
-                    out["parity"][mo] = {"ticks": pt, "digest_match": all(ok), "digest_match_per_tick": ok, "arrays": 8,
+                    ok = [tuple(cpu_dig[tk]) == tuple(m["digests"][tk]) for tk in cmp]
+                    out["parity"][mo] = {"ticks": cmp, "digest_match": all(ok), "digest_match_per_tick": ok, "arrays": 8,
                                          "what": "sim_state_digest of the GPU run right before the timed region AND right behind its last timed tick (rows, "
                                                  "queues, packets in flight, views, both rings, slot map + liveness, query tables) against the CPU "
                                                  "oracle rolled through the same schedule to the same ticks (oracle/liboracle.so, the checker): the "
                                                  "timed launches themselves are covered",
-                                         "gpu": {str(tk): [f"{x:016x}" for x in m["digests"][tk]] for tk in pt},
-                                         "oracle": {str(tk): [f"{x:016x}" for x in cpu_dig[tk]] for tk in pt}}
+                                         "gpu": {str(tk): [f"{x:016x}" for x in m["digests"][tk]] for tk in cmp},
+                                         "oracle": {str(tk): [f"{x:016x}" for x in cpu_dig[tk]] for tk in cmp}}
+                    if len(cmp) < len(pt):
+                        out["parity"][mo]["not_compared"] = {"ticks": [tk for tk in pt if tk not in cmp], "why": why}
             out["parity"]["digest_match"] = all(v.get("digest_match") is not False for v in out["parity"].values() if isinstance(v, dict))
             out["parity"]["ticks"] = head["parity_ticks"]
+            skipped = sorted({tk for v in out["parity"].values() if isinstance(v, dict) for tk in v.get("not_compared", {}).get("ticks", [])})
+            if skipped:
+                out["parity"]["not_compared"] = skipped
         emit_result(out)
     progress.done = True
     if world > 1 or args.force_sharded:

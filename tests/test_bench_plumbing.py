@@ -21,7 +21,7 @@ def _worker(rank, world, port, q, extra=()):
 
     try:
         args = bench.parse_args(["--gpus", str(world), "--steps", "20", "--warmup", "10", "--nodes-per-gpu", "2048",
-                                 "--view-slots", "64", "--ring", "32", "--no-cpu-baseline", "--allow-drops", *extra])
+                                 "--view-slots", "64", "--ring", "32", "--no-cpu-baseline", "--allow-drops", "--full", *extra])
         out = bench.run(args, lib=load_oracle(), dev=torch.device("cpu"), backend="gloo")
         q.put((rank, json.dumps(out) if out is not None else "null"))
     except BaseException as e:  # noqa: BLE001
@@ -104,7 +104,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "tests", "_bench_cpu_rehearsal.py"), "--gpus", "2", "--steps", "10", "--warmup", "5",
            "--preroll", "40", "--nodes-per-gpu", "2048", "--view-slots", "64", "--ring", "32", "--no-cpu-baseline", "--no-convergence",
-           "--allow-drops", "--backend", "gloo"]
+           "--allow-drops", "--backend", "gloo", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -130,3 +130,90 @@ def test_bench_reports_a_dead_rank_instead_of_hanging():
     assert p.returncode != 0
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and "error" in json.loads(lines[0]) and json.loads(lines[0])["value"] is None
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_what_it_computed(tmp_path, monkeypatch):
+    """Without --full a run measures the headline model alone; --dump-outputs writes the state of the headline cluster right
+    after its last timed tick, the same in a plain and a --full run, and that state is what the workload rolled to that tick
+    gives (digest)."""
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import bench
+    from serf_amd import _ffi
+    from tests._oracle import load_oracle
+
+    lib = load_oracle()
+    common = ["--gpus", "1", "--steps", "12", "--warmup", "4", "--preroll", "40", "--nodes-per-gpu", "2048", "--view-slots", "64",
+              "--ring", "32", "--allow-drops"]
+    plain = bench.parse_args(common + ["--dump-outputs", str(tmp_path / "plain")])
+    out = bench.run(plain, lib=lib, dev=torch.device("cpu"), backend="gloo")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out, key
+    assert out["steps"] == 12 and out["value"] > 0 and out["ms_per_step"] > 0 and out["config"]["fanout_model"] == "krandomnodes"
+    assert list(out["fanout_models"]) == ["krandomnodes"] and out["rounds_to_99"] is None
+    for key in ("long_window", "cpu_baseline", "parity", "second_load"):
+        assert key not in out, key
+    full = bench.parse_args(common + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    out_full = bench.run(full, lib=lib, dev=torch.device("cpu"), backend="gloo")
+    assert set(out_full["fanout_models"]) == {"krandomnodes", "bijection"} and out_full["rounds_to_99"]["n"] > 0
+
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == ["cluster_stats.npy", "digest.npy", "members.npy", "queue.npy", "rows.npy"]
+    assert sorted(os.listdir(tmp_path / "full")) == names
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
+        assert a.dtype == np.float64 and a.size > 0, name
+        assert np.array_equal(a, b), f"{name}: a plain and a --full run dumped different outputs"
+        total += a.nbytes
+    assert total <= 64 << 20
+    cs = np.load(tmp_path / "plain" / "cluster_stats.npy")
+    assert cs[-1] == 40 + 4 + 12, "the dump is taken right after the last timed tick"
+
+    kw, ops = bench.workload(plain, 2048, "krandomnodes")
+    sim = _ffi.Sim(lib, _ffi.make_config(2048, **kw))
+    for o in ops:
+        sim.inject(*o)
+    sim.step(40 + 4 + 12)
+    want = [[x >> 32, x & 0xFFFFFFFF] for x in sim.digest()]
+    rows = sim.dump(_ffi.ARR_ROWS)
+    sim.close()
+    assert np.load(tmp_path / "plain" / "digest.npy").tolist() == want
+    got = np.load(tmp_path / "plain" / "rows.npy")
+    assert got.shape == (2048, 36) and len(rows) == 2048   # (2 048 nodes: the sample is all of them, in order)
+    assert got[:, 0].tolist() == (rows["clock"] >> np.uint64(32)).tolist() and got[:, 1].tolist() == (rows["clock"] & np.uint64(0xFFFFFFFF)).tolist()
+    assert got[:, 10].tolist() == rows["flags"].tolist() and got[:, 20:].tolist() == rows["susp"].tolist()
+
+
+def test_cpu_baseline_leaves_out_the_parity_ticks_it_cannot_reach_in_its_budget():
+    """bench.py --full on a long timed region: the oracle cannot follow the GPU to the end of it in its CPU budget.  What it
+    cannot reach is reported as not compared (digest None, a reason) instead of ending the run; what it reaches is compared."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from serf_amd import _ffi
+    from tests._oracle import load_oracle
+
+    args = bench.parse_args(["--steps", "12", "--warmup", "4", "--preroll", "40", "--nodes-per-gpu", "2048", "--view-slots", "64",
+                             "--ring", "32"])
+    args.cpu_thread_curve = False
+    res, dig, why = bench.cpu_baseline(args, "krandomnodes", [44, 56], seconds_budget=120.0)
+    assert res["value"] > 0 and dig[44] is not None and dig[56] is not None and why is None
+    kw, ops = bench.workload(args, 2048, "krandomnodes")
+    sim = _ffi.Sim(load_oracle(), _ffi.make_config(2048, **kw))
+    for o in ops:
+        sim.inject(*o)
+    sim.step(44)
+    assert tuple(dig[44]) == sim.digest()
+    sim.step(12)
+    assert tuple(dig[56]) == sim.digest()
+    sim.close()
+
+    far = 10 ** 7   # (hours of oracle time: never begun)
+    res, dig2, why = bench.cpu_baseline(args, "krandomnodes", [44, far], seconds_budget=20.0)
+    assert res["value"] > 0 and dig2[44] == dig[44] and dig2[far] is None and "not rolled" in why
+    res, dig3, why = bench.cpu_baseline(args, "krandomnodes", [far, far + 12], seconds_budget=0.5)
+    assert res is None and dig3 == {far: None, far + 12: None} and "not rolled" in why
