@@ -112,6 +112,26 @@ ABI_SYMBOLS = ("create", "destroy", "set_stream", "join", "leave", "force_leave"
                "exchange_unique_id", "exchange_init", "exchange_chunk", "exchange_wait", "exchange_library",
                "abi_version", "backend_name")
 
+# include/serf_sim_track.h: device-resident trackers.  An extension with a version of its own, bound only when the loaded
+# library exports it (the product does; the CPU oracle, the checker, has none)
+TRACK_SYMBOLS = ("track_add", "track_remove", "track_read", "track_active", "track_version")
+TRACK_MAX, TRACK_NEVER = 1024, 0xFFFFFFFF
+TRK_RUMOUR, TRK_MEMBER = 1, 2
+
+
+class Tracker(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32), ("min_inc", C.c_uint32),
+                ("ltime", C.c_uint64), ("start_tick", C.c_uint32), ("max_age", C.c_uint32)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("first", C.c_uint32), ("half", C.c_uint32), ("p90", C.c_uint32), ("p99", C.c_uint32), ("all", C.c_uint32),
+                ("evaluated", C.c_uint32), ("peak", C.c_uint64), ("last", C.c_uint64), ("last_up", C.c_uint64),
+                ("state", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "pad"}
+
 
 def make_config(n_nodes, *, fanout=3, vshards=1, shard_rank=0, shard_count=1, view_slots=0,
                 event_ring=512, query_ring=512, retransmit_mult=4, probe_interval=0,
@@ -147,6 +167,14 @@ def make_config(n_nodes, *, fanout=3, vshards=1, shard_rank=0, shard_count=1, vi
     if prune_delay:
         cfg.flags |= CF_PRUNE_DELAY    # handle_prune's wait (base.rs:1628-1653): a Leaving member's forced erase comes leave_delay ticks later
     return cfg
+
+
+def rumour_tracker(kind, key, ltime, start=0, max_age=0):
+    return Tracker(TRK_RUMOUR, kind, key, 0, ltime, start, max_age)
+
+
+def member_tracker(subject, status_mask, swim_mask=0, min_inc=0, start=0, max_age=0):
+    return Tracker(TRK_MEMBER, subject, (status_mask & 0xFF) | (swim_mask << 8), min_inc, 0, start, max_age)
 
 
 class SimLib:
@@ -230,6 +258,19 @@ class SimLib:
             fn = getattr(self.dll, prefix + name)  # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             self.f[name] = fn
+        track = {
+            "track_add": (C.c_int, [H, C.POINTER(Tracker), u32, C.POINTER(u32)]),
+            "track_remove": (C.c_int, [H, C.POINTER(u32), u32]),
+            "track_read": (C.c_int, [H, C.POINTER(u32), u32, C.POINTER(TrackResult)]),
+            "track_active": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
+            "track_version": (u32, []),
+        }
+        self.has_trackers = all(hasattr(self.dll, prefix + name) for name in TRACK_SYMBOLS)
+        if self.has_trackers:
+            for name in TRACK_SYMBOLS:
+                fn = getattr(self.dll, prefix + name)
+                fn.restype, fn.argtypes = track[name]
+                self.f[name] = fn
 
     def backend_name(self):
         return self.f["backend_name"]().decode()
@@ -249,6 +290,10 @@ class SimLib:
 
     def abi_version(self):
         return self.f["abi_version"]()
+
+    def track_version(self):
+        """SIM_TRACK_VERSION of include/serf_sim_track.h, or None when the library has no trackers."""
+        return self.f["track_version"]() if self.has_trackers else None
 
 
 class Sim:
@@ -413,6 +458,48 @@ class Sim:
         seen, up = (C.c_uint64 * max(1, n))(), C.c_uint64()
         self._ck(self.lib.f["convergence_many"](self.h, n, kinds, keys, lts, seen, C.byref(up)), "sim_convergence_many")
         return [int(x) for x in seen[:n]], up.value
+
+    # ---- device-resident trackers (include/serf_sim_track.h) ----
+    def _track_fn(self, name):
+        if not self.lib.has_trackers:
+            raise NotImplementedError(f"{self.lib.path} exports no sim_track_* (include/serf_sim_track.h)")
+        return self.lib.f[name]
+
+    def track_add(self, trackers):
+        """Registers a list of Tracker; returns their ids (stable until track_remove)."""
+        n = len(trackers)
+        arr = (Tracker * max(1, n))(*trackers)
+        ids = (C.c_uint32 * max(1, n))()
+        self._ck(self._track_fn("track_add")(self.h, arr, n, ids), "sim_track_add")
+        return list(ids[:n])
+
+    def track_remove(self, ids):
+        ids = list(ids)
+        arr = (C.c_uint32 * max(1, len(ids)))(*ids)
+        self._ck(self._track_fn("track_remove")(self.h, arr, len(ids)), "sim_track_remove")
+
+    def track_read(self, ids):
+        """[TrackResult] of the named trackers; waits for the handle's stream."""
+        ids = list(ids)
+        arr = (C.c_uint32 * max(1, len(ids)))(*ids)
+        out = (TrackResult * max(1, len(ids)))()
+        self._ck(self._track_fn("track_read")(self.h, arr, len(ids), out), "sim_track_read")
+        return list(out[:len(ids)])
+
+    def track_active(self):
+        """(registered, of which not retired)."""
+        r, a = C.c_uint32(), C.c_uint32()
+        self._ck(self._track_fn("track_active")(self.h, C.byref(r), C.byref(a)), "sim_track_active")
+        return r.value, a.value
+
+    def track_rumour(self, kind, key, ltime, start=0, max_age=0):
+        """One RUMOUR tracker (kind = K_JOIN / K_LEAVE / K_EVENT / K_QUERY, as for convergence); returns its id."""
+        return self.track_add([rumour_tracker(kind, key, ltime, start, max_age)])[0]
+
+    def track_member(self, subject, status_mask, swim_mask=0, min_inc=0, start=0, max_age=0):
+        """One MEMBER tracker: running nodes whose entry of `subject` has a MemberStatus in status_mask (bit i = STATUS_i)
+        or, when known, a memberlist state in swim_mask (bit j = SWIM_j), at incarnation >= min_inc; returns its id."""
+        return self.track_add([member_tracker(subject, status_mask, swim_mask, min_inc, start, max_age)])[0]
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

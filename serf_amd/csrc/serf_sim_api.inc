@@ -18,6 +18,7 @@ int sim_destroy(sim_handle* h) {
   if (!h) return SIM_EINVAL;
   (void)hipStreamSynchronize(h->stream);
   if (h->xstream) (void)hipStreamSynchronize(h->xstream);
+  if (h->trk) track_destroy(h);
   if (h->xcomm) (void)ncclCommDestroy(h->xcomm);
   if (h->xstream) (void)hipStreamDestroy(h->xstream);
   if (h->xev_go) (void)hipEventDestroy(h->xev_go);
@@ -1226,6 +1227,7 @@ int sim_step_end(sim_handle* h) {
     h->sreq_on_dispatch = false;
     h->sreq_tick[t % 3] = t;
   }
+  if (h->trk) return track_step_end(h);  // registered trackers: the tick's evaluation follows it on the stream
   return SIM_OK;
 }
 // the list of one finished tick out of its buffer (sorted by prober); marks it read

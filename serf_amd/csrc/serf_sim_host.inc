@@ -137,7 +137,11 @@ struct sim_handle {
   LazyPlanes lz_view, lz_ev, lz_q;
   u64 ev_hi, q_hi;
   u32* deep_seen;  // pinned: the longest deep list any launch has had (deep_queue_kernel keeps it; sizes that kernel's grid)
+  struct TrackState* trk = nullptr;  // device-resident trackers (serf_sim_track.inc); null until the first sim_track_add
 };
+// serf_sim_track.inc: the hooks of sim_step_end / sim_destroy (called only when h->trk)
+static int track_step_end(sim_handle* h);
+static void track_destroy(sim_handle* h);
 
 #define HCHECK(x)                                                                        \
   do {                                                                                   \

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/serf_sim.h"
+#include "../../include/serf_sim_track.h"
 #include "wire.hpp"
 
 namespace serf {
@@ -186,6 +187,31 @@ class Cluster {
     uint64_t seen = 0, up = 0;
     check(sim_convergence(h_, kind, key, ltime, &seen, &up), "sim_convergence");
     return up ? (double)seen / (double)up : 0.0;
+  }
+  // device-resident trackers (include/serf_sim_track.h): dissemination / detection latency without a poll per tick — register,
+  // step(n) with n as large as the run, read.  HIP library only (the CPU oracle exports no sim_track_*).
+  std::vector<uint32_t> track_add(const std::vector<sim_tracker>& t) {
+    std::vector<uint32_t> ids(t.size());
+    check(sim_track_add(h_, t.data(), (uint32_t)t.size(), ids.data()), "sim_track_add");
+    return ids;
+  }
+  void track_remove(const std::vector<uint32_t>& ids) { check(sim_track_remove(h_, ids.data(), (uint32_t)ids.size()), "sim_track_remove"); }
+  std::vector<sim_track_result> track_read(const std::vector<uint32_t>& ids) {
+    std::vector<sim_track_result> out(ids.size());
+    check(sim_track_read(h_, ids.data(), (uint32_t)ids.size(), out.data()), "sim_track_read");
+    return out;
+  }
+  std::pair<uint32_t, uint32_t> track_active() {  // (registered, of which not retired)
+    uint32_t r = 0, a = 0;
+    check(sim_track_active(h_, &r, &a), "sim_track_active");
+    return {r, a};
+  }
+  static sim_tracker rumour_tracker(uint32_t kind, uint32_t key, uint64_t ltime, uint32_t start = 0, uint32_t max_age = 0) {
+    return sim_tracker{SIM_TRK_RUMOUR, kind, key, 0, ltime, start, max_age};
+  }
+  static sim_tracker member_tracker(uint32_t subject, uint32_t status_mask, uint32_t swim_mask = 0, uint32_t min_inc = 0,
+                                    uint32_t start = 0, uint32_t max_age = 0) {
+    return sim_tracker{SIM_TRK_MEMBER, subject, (status_mask & 0xFFu) | (swim_mask << 8), min_inc, 0, start, max_age};
   }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {

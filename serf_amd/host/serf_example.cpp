@@ -15,6 +15,10 @@ int main(int argc, char** argv) {
     s7.user_event(/*event_key=*/42, /*encoded_len=*/64);
     cl.node(9).leave();
     cl.crash(11, /*at_tick=*/2);
+    // followed on the device, read once at the end: who suspects node 11 (or worse), who has declared it failed
+    std::vector<uint32_t> trk = cl.track_add({
+        serf::Cluster::member_tracker(11, 1u << SIM_STATUS_FAILED, 1u << SIM_SWIM_SUSPECT | 1u << SIM_SWIM_DEAD, 0, /*start=*/2),
+        serf::Cluster::member_tracker(11, 1u << SIM_STATUS_FAILED, 0, 0, /*start=*/2)});
     uint32_t rounds = 0;
     while (cl.convergence(SIM_K_EVENT, 42, 1) < 0.99 && rounds < 200) { cl.step(); ++rounds; }
     printf("user event reached 99%% of %u nodes after %u rounds\n", n, rounds);
@@ -31,6 +35,10 @@ int main(int argc, char** argv) {
     serf::Stats st = s0.stats();
     printf("node 0: members %u failed %u left %u, clocks %llu/%llu/%llu\n", st.members, st.failed, st.left,
            (unsigned long long)st.member_time, (unsigned long long)st.event_time, (unsigned long long)st.query_time);
+    std::vector<sim_track_result> tr = cl.track_read(trk);
+    printf("crash of node 11 at tick 2: first suspicion at tick %u, declared failed by 99%% at tick %u, by all at tick %u\n",
+           tr[0].first, tr[1].p99, tr[1].all);
+    if (tr[0].first == SIM_TRACK_NEVER || tr[1].p99 == SIM_TRACK_NEVER || tr[0].first > tr[1].p99) return 1;
     for (const serf::Event& e : cl.drain_events())
       printf("  tick %u observer %u event %u key %u ltime %llu\n", e.tick, e.observer, e.type, e.key, (unsigned long long)e.ltime);
     return st.failed == 1 && st.left == 1 ? 0 : 1;

@@ -10,7 +10,17 @@ gossip rounds until >= 99 % of the running nodes have applied it is recorded.  T
 hit (`model_bound_drops` == 0).  The pace of the churn is set by the model's per-node capacity: SIM_S = 16 suspicion timers
 (a crashed node is a running suspicion at every node for ~125 ticks); the queue holds 64 entries (r6).
 
-Needs an MI355X.  Writes one JSON (default profiles/r03_config4_churn5_loss1_swim.json)."""
+`--tracker`: the same kind of run followed by DEVICE-RESIDENT TRACKERS (include/serf_sim_track.h) instead of a host poll per
+tick.  Crashes are drawn with a per-tick probability (`--crash-prob`; a draw is skipped while `--crash-cap` crashed nodes are
+still inside their suspicion window: what SIM_S = 16 timers per node allow without drops), user events are injected in bursts
+WHILE the churn runs (many outstanding at once), and the run advances in one sim_step per stretch between two bursts.  Output:
+histograms of the rounds until 50 / 90 / 99 / 100 % of the running nodes have applied an event, of the ticks from a crash to the
+first suspicion and to "declared failed by 99 %", and the number of sampled never-crashed nodes that anybody ever suspected.
+The run of profiles/r07_config4_tracker.json (zero drops at 2 Mi nodes): --random-fanout --pkt-records 16 --tcp-fallback --nacks
+--reconnect-interval 150 --gossip-to-the-dead 150 --rumors 560 --burst 4 --crash-prob 0.1 --crash-cap 12.  Bursts have to lie further
+apart than an event needs to reach everybody: origins that have not seen the last burst give the next one the same Lamport time.
+
+Needs an MI355X.  Writes one JSON (default profiles/r03_config4_churn5_loss1_swim.json; --tracker: profiles/r07_config4_tracker.json)."""
 import argparse
 import json
 import os
@@ -19,6 +29,128 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def hist(values):
+    import numpy as np
+    return {int(k): int(v) for k, v in zip(*np.unique(np.asarray(values, dtype=np.int64), return_counts=True))} if len(values) else {}
+
+
+def run_tracker(args, sim, lib):
+    """The --tracker run: everything the host does happens between two long sim_step calls."""
+    import math
+
+    import numpy as np
+    from serf_amd import _ffi
+    n, total = args.nodes, args.ticks
+    NEVER = _ffi.TRACK_NEVER
+    FAILED, SUSPECT_OR_DEAD = 1 << _ffi.STATUS_FAILED, 1 << _ffi.SWIM_SUSPECT | 1 << _ffi.SWIM_DEAD
+    rng = np.random.default_rng(5)
+    # a crashed node is a running suspicion at every node for about the minimum suspicion timeout (memberlist: suspicion_mult x
+    # log10 n x probe interval; make_config's suspicion_mult is 4) and some ticks until the first probe finds it
+    window = int(4 * max(1.0, math.log10(n)) * args.probe_interval) + 4 * args.probe_interval
+    crashes, recent, gone = [], [], set()   # (tick, node)
+    for t in range(20, total - args.down - 50):
+        recent = [x for x in recent if x + window > t]
+        if rng.random() < args.crash_prob and len(recent) < args.crash_cap:
+            node = int(rng.integers(0, n))
+            while node in gone:
+                node = int(rng.integers(0, n))
+            gone.add(node)
+            crashes.append((t, node))
+            recent.append(t)
+    for t, node in crashes:
+        sim.inject(t, _ffi.OP_CRASH, node)
+        sim.inject(t + args.down, _ffi.OP_JOIN, node)
+    sample = []
+    while len(sample) < args.fp_sample:
+        x = int(rng.integers(0, n))
+        if x not in gone and x not in sample:
+            sample.append(x)
+    fp_ids = sim.track_add([_ffi.member_tracker(x, FAILED, SUSPECT_OR_DEAD) for x in sample]) if sample else []
+    crash_ids = {}   # node -> (tick, suspect+ id, failed id); registered up front in batches that fit beside the events'
+    bursts = max(1, args.rumors // args.burst)
+    every = max(1, (total - 100) // bursts)
+    live_ev, done_ev, done_cr = [], [], []   # (id, inject tick) / (inject tick, result) / (crash tick, suspect+, failed)
+    ci = 0
+    t0 = time.perf_counter()
+    stretches = 0
+
+    def harvest(now):
+        nonlocal live_ev
+        over = [(i, t) for i, t in live_ev if t + args.max_rounds <= now]
+        if over:
+            for (i, t), r in zip(over, sim.track_read([i for i, _ in over])):
+                done_ev.append((t, r.as_dict()))
+            sim.track_remove([i for i, _ in over])
+            live_ev = [(i, t) for i, t in live_ev if t + args.max_rounds > now]
+        ended = [node for node, (t, a, b) in crash_ids.items() if t + args.down <= now]
+        if ended:
+            ids = [x for node in ended for x in crash_ids[node][1:]]
+            rs = sim.track_read(ids)
+            for k, node in enumerate(ended):
+                done_cr.append((crash_ids[node][0], rs[2 * k].as_dict(), rs[2 * k + 1].as_dict()))
+                del crash_ids[node]
+            sim.track_remove(ids)
+
+    while sim.tick < total:
+        t = sim.tick
+        harvest(t)
+        # the crashes of the coming stretch get their two trackers now (their windows open at the crash)
+        batch = []
+        while ci < len(crashes) and crashes[ci][0] < t + every:
+            batch.append(crashes[ci])
+            ci += 1
+        if batch:
+            ids = sim.track_add([tr for ct, node in batch for tr in (_ffi.member_tracker(node, FAILED, SUSPECT_OR_DEAD, start=ct, max_age=args.down),
+                                                                     _ffi.member_tracker(node, FAILED, start=ct, max_age=args.down))])
+            for k, (ct, node) in enumerate(batch):
+                crash_ids[node] = (ct, ids[2 * k], ids[2 * k + 1])
+        if 50 <= t < total - args.max_rounds:
+            specs, keys = [], []
+            for _ in range(args.burst):
+                node = int(rng.integers(0, n))
+                while node in gone:
+                    node = int(rng.integers(0, n))
+                key = 0x40000000 + len(done_ev) + len(live_ev) + len(keys)
+                specs.append(_ffi.rumour_tracker(_ffi.K_EVENT, key, sim.stats(node).event_time, max_age=args.max_rounds))
+                keys.append((node, key))
+            live_ev += [(i, t) for i in sim.track_add(specs)]
+            for node, key in keys:
+                sim.user_event(node, key, 64)
+        sim.step(min(every, total - t))     # ONE call per stretch; nothing is read back inside it
+        stretches += 1
+    sim.sync()
+    dt = time.perf_counter() - t0
+    harvest(sim.tick + args.max_rounds + args.down)
+    fp = [r.as_dict() for r in sim.track_read(fp_ids)] if fp_ids else []
+    cs = sim.cluster_stats()
+
+    def rounds(name):
+        return [r[name] - t for t, r in done_ev if r[name] != NEVER]
+    out = {
+        "what": "BASELINE configs[4] on one GPU followed by device-resident trackers: crashes with a per-tick probability, user events in bursts "
+                "while the churn runs, one sim_step per stretch; latencies in ticks",
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib")}, "backend": lib.backend_name(),
+        "ticks": int(sim.tick), "sim_step_calls": stretches, "crashes": len(crashes), "suspicion_window_assumed": window,
+        "events": len(done_ev),
+        "rounds_to": {k: {"histogram": hist(rounds(f)), "not_reached": sum(r[f] == NEVER for _, r in done_ev)}
+                      for k, f in (("50", "half"), ("90", "p90"), ("99", "p99"), ("100", "all"))},
+        "detection": {
+            "crashes_followed": len(done_cr),
+            "first_suspicion_after_crash": {"histogram": hist([a["first"] - t for t, a, b in done_cr if a["first"] != NEVER]),
+                                            "never": sum(a["first"] == NEVER for t, a, b in done_cr)},
+            "declared_failed_by_99pct_after_crash": {"histogram": hist([b["p99"] - t for t, a, b in done_cr if b["p99"] != NEVER]),
+                                                     "never": sum(b["p99"] == NEVER for t, a, b in done_cr)}},
+        "false_positives": {"sampled_never_crashed_nodes": len(fp), "ever_suspected_or_worse_by_anybody": sum(r["peak"] > 0 for r in fp),
+                            "largest_number_of_accusers": max([r["peak"] for r in fp], default=0)},
+        "model_bound_drops": int(cs["overflow"]), "ops_dropped_no_slot": int(cs["ops_dropped"]),
+        "view_slots_recycled": int(cs["slots_recycled"]), "nodes_up_at_end": int(cs["up"]),
+        "wall_s": dt, "member_ticks_per_s_incl_tracking": n * int(sim.tick) / dt,
+    }
+    json.dump(out, open(args.out, "w"), indent=1)
+    print(json.dumps({k: out[k] for k in ("ticks", "sim_step_calls", "crashes", "events", "false_positives", "model_bound_drops", "ops_dropped_no_slot", "wall_s")}), "->", args.out)
+    print(json.dumps({"rounds_to_99": out["rounds_to"]["99"], "detection": out["detection"]}))
 
 
 def main():
@@ -46,8 +178,16 @@ def main():
     ap.add_argument("--vshards", type=int, default=1, help="virtual shards of the fan-out map (the shape of one rank's share of a V-way sharded cluster)")
     ap.add_argument("--chunks", type=int, default=0, help="sender chunks per shard (the chunk-wise exchange's layout)")
     ap.add_argument("--lib", default=None, help="oracle: run the CPU oracle instead (small sizes; for checking the tool)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r03_config4_churn5_loss1_swim.json"))
+    ap.add_argument("--tracker", action="store_true", help="follow the run with device-resident trackers (see above) instead of polling every tick")
+    ap.add_argument("--ticks", type=int, default=4000, help="--tracker: length of the run")
+    ap.add_argument("--crash-prob", type=float, default=1 / 24, help="--tracker: probability per tick that one running node crashes")
+    ap.add_argument("--crash-cap", type=int, default=10, help="--tracker: crashes inside one suspicion window (SIM_S = 16 timers per node, some are false suspicions)")
+    ap.add_argument("--burst", type=int, default=4, help="--tracker: user events injected at once (they share a Lamport time, hence a ring bucket of SIM_C = 6 keys: more than 6 use up the overflow rows)")
+    ap.add_argument("--fp-sample", type=int, default=64, help="--tracker: never-crashed nodes watched for false suspicions")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
 
     import numpy as np
     from serf_amd import _ffi
@@ -67,6 +207,8 @@ def main():
               **({"flags": _ffi.CF_BASELINE_JOINED | _ffi.CF_RANDOM_FANOUT} if args.random_fanout else {}),
               join_sync=True)   # Serf::join = memberlist.join: the re-joining node syncs with a peer (SIM_CF_JOIN_SYNC)
     sim = _ffi.Sim(lib, _ffi.make_config(n, **kw))
+    if args.tracker:
+        return run_tracker(args, sim, lib)
     rng = np.random.default_rng(5)
     n_churn = int(n * args.churn_frac)
     total = 20 + n_churn * args.churn_every + args.down + 400
@@ -120,7 +262,8 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib")}, "backend": lib.backend_name(),
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample")},
+        "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
                          "max": int(r.max()), "min": int(r.min()), "not_converged": int((r > args.max_rounds).sum())},
