@@ -119,6 +119,21 @@ TRACK_MAX, TRACK_NEVER = 1024, 0xFFFFFFFF
 TRK_RUMOUR, TRK_MEMBER = 1, 2
 
 
+# include/serf_sim_series.h: device-resident time series (cluster gauges sampled behind a tick).  Likewise an extension with a
+# version of its own, bound only when the loaded library exports it
+SERIES_SYMBOLS = ("series_start", "series_count", "series_read", "series_stop", "series_version")
+SERIES_WORDS, SERIES_MAX_SAMPLES = 64, 1 << 20
+# one sample as a numpy record: the table of include/serf_sim_series.h, 64 little-endian 64-bit words
+SERIES_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("state", "<u8", (4,)), ("queued", "<u8", (4,)),
+                         ("depth_bins", "<u8", (8,)), ("max_depth", "<u8"), ("awareness", "<u8", (8,)),
+                         ("timers", "<u8"), ("nodes_with_timers", "<u8"), ("n_failed", "<u8"), ("n_left", "<u8"),
+                         ("n_known_min", "<u8"), ("n_known_max", "<u8"), ("clock_min", "<u8"), ("clock_max", "<u8"),
+                         ("event_clock_min", "<u8"), ("event_clock_max", "<u8"), ("query_clock_min", "<u8"),
+                         ("query_clock_max", "<u8"), ("overflow", "<u8"), ("packets", "<u8"), ("records", "<u8", (7,)),
+                         ("len64", "<u8"), ("reserved", "<u8", (15,))])
+assert SERIES_DTYPE.itemsize == 8 * SERIES_WORDS
+
+
 class Tracker(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32), ("min_inc", C.c_uint32),
                 ("ltime", C.c_uint64), ("start_tick", C.c_uint32), ("max_age", C.c_uint32)]
@@ -271,6 +286,19 @@ class SimLib:
                 fn = getattr(self.dll, prefix + name)
                 fn.restype, fn.argtypes = track[name]
                 self.f[name] = fn
+        series = {
+            "series_start": (C.c_int, [H, u32, u32, u32]),
+            "series_count": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
+            "series_read": (C.c_int, [H, u32, u32, vp, C.POINTER(u32)]),
+            "series_stop": (C.c_int, [H]),
+            "series_version": (u32, []),
+        }
+        self.has_series = all(hasattr(self.dll, prefix + name) for name in SERIES_SYMBOLS)
+        if self.has_series:
+            for name in SERIES_SYMBOLS:
+                fn = getattr(self.dll, prefix + name)
+                fn.restype, fn.argtypes = series[name]
+                self.f[name] = fn
 
     def backend_name(self):
         return self.f["backend_name"]().decode()
@@ -294,6 +322,10 @@ class SimLib:
     def track_version(self):
         """SIM_TRACK_VERSION of include/serf_sim_track.h, or None when the library has no trackers."""
         return self.f["track_version"]() if self.has_trackers else None
+
+    def series_version(self):
+        """SIM_SERIES_VERSION of include/serf_sim_series.h, or None when the library has no series."""
+        return self.f["series_version"]() if self.has_series else None
 
 
 class Sim:
@@ -500,6 +532,37 @@ class Sim:
         """One MEMBER tracker: running nodes whose entry of `subject` has a MemberStatus in status_mask (bit i = STATUS_i)
         or, when known, a memberlist state in swim_mask (bit j = SWIM_j), at incarnation >= min_inc; returns its id."""
         return self.track_add([member_tracker(subject, status_mask, swim_mask, min_inc, start, max_age)])[0]
+
+    # ---- device-resident time series (include/serf_sim_series.h) ----
+    def _series_fn(self, name):
+        if not self.lib.has_series:
+            raise NotImplementedError(f"{self.lib.path} exports no sim_series_* (include/serf_sim_series.h)")
+        return self.lib.f[name]
+
+    def series_start(self, first_tick=0, period=1, capacity=1 << 16):
+        """Starts sampling: behind every tick t >= first_tick with (t - first_tick) % period == 0, until `capacity` samples
+        are held (a first_tick that has passed means "now")."""
+        self._ck(self._series_fn("series_start")(self.h, first_tick, period, capacity), "sim_series_start")
+
+    def series_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        t, d = C.c_uint32(), C.c_uint32()
+        self._ck(self._series_fn("series_count")(self.h, C.byref(t), C.byref(d)), "sim_series_count")
+        return t.value, d.value
+
+    def series_read(self, first=0, n=None):
+        """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as a numpy array of SERIES_DTYPE;
+        waits for the handle's stream."""
+        if n is None:
+            n = max(0, self.series_count()[0] - first)
+        out = np.zeros(max(1, n), SERIES_DTYPE)
+        got = C.c_uint32()
+        self._ck(self._series_fn("series_read")(self.h, first, n, out.ctypes.data, C.byref(got)), "sim_series_read")
+        return out[:got.value]
+
+    def series_stop(self):
+        """Ends the series and frees its buffers (the samples are gone)."""
+        self._ck(self._series_fn("series_stop")(self.h), "sim_series_stop")
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

@@ -19,6 +19,7 @@ int sim_destroy(sim_handle* h) {
   (void)hipStreamSynchronize(h->stream);
   if (h->xstream) (void)hipStreamSynchronize(h->xstream);
   if (h->trk) track_destroy(h);
+  if (h->ser) series_destroy(h);
   if (h->xcomm) (void)ncclCommDestroy(h->xcomm);
   if (h->xstream) (void)hipStreamDestroy(h->xstream);
   if (h->xev_go) (void)hipEventDestroy(h->xev_go);
@@ -1227,7 +1228,8 @@ int sim_step_end(sim_handle* h) {
     h->sreq_on_dispatch = false;
     h->sreq_tick[t % 3] = t;
   }
-  if (h->trk) return track_step_end(h);  // registered trackers: the tick's evaluation follows it on the stream
+  if (h->trk) { if (int rc = track_step_end(h)) return rc; }  // registered trackers: the tick's evaluation follows it on the stream
+  if (h->ser) return series_step_end(h);  // a running series: the tick's sample, when one is due, likewise
   return SIM_OK;
 }
 // the list of one finished tick out of its buffer (sorted by prober); marks it read

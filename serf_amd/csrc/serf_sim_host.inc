@@ -138,10 +138,14 @@ struct sim_handle {
   u64 ev_hi, q_hi;
   u32* deep_seen;  // pinned: the longest deep list any launch has had (deep_queue_kernel keeps it; sizes that kernel's grid)
   struct TrackState* trk = nullptr;  // device-resident trackers (serf_sim_track.inc); null until the first sim_track_add
+  struct SeriesState* ser = nullptr;  // device-resident time series (serf_sim_series.inc); null unless one is running
 };
 // serf_sim_track.inc: the hooks of sim_step_end / sim_destroy (called only when h->trk)
 static int track_step_end(sim_handle* h);
 static void track_destroy(sim_handle* h);
+// serf_sim_series.inc: likewise (called only when h->ser)
+static int series_step_end(sim_handle* h);
+static void series_destroy(sim_handle* h);
 
 #define HCHECK(x)                                                                        \
   do {                                                                                   \

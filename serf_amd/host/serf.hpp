@@ -19,6 +19,7 @@
 
 #include "../../include/serf_sim.h"
 #include "../../include/serf_sim_track.h"
+#include "../../include/serf_sim_series.h"
 #include "wire.hpp"
 
 namespace serf {
@@ -213,6 +214,26 @@ class Cluster {
                                     uint32_t start = 0, uint32_t max_age = 0) {
     return sim_tracker{SIM_TRK_MEMBER, subject, (status_mask & 0xFFu) | (swim_mask << 8), min_inc, 0, start, max_age};
   }
+  // device-resident time series (include/serf_sim_series.h): one sample of cluster gauges (queue depths by class and as a histogram,
+  // health scores, suspicion timers, clock spread, what the packets in flight carry) behind every period-th tick — start,
+  // step(n) with n as large as the run, read.  HIP library only (the CPU oracle exports no sim_series_*).
+  void series_start(uint32_t first_tick = 0, uint32_t period = 1, uint32_t capacity = 1u << 16) {
+    check(sim_series_start(h_, first_tick, period, capacity), "sim_series_start");
+  }
+  std::pair<uint32_t, uint32_t> series_count() const {  // (samples taken, dropped with the buffer full); waits for nothing
+    uint32_t t = 0, d = 0;
+    check(sim_series_count(h_, &t, &d), "sim_series_count");
+    return {t, d};
+  }
+  std::vector<sim_series_sample> series_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    if (n == 0xFFFFFFFFu) { const uint32_t t = series_count().first; n = t > first ? t - first : 0; }
+    std::vector<sim_series_sample> out(n ? n : 1);
+    uint32_t got = 0;
+    check(sim_series_read(h_, first, n, out.data(), &got), "sim_series_read");
+    out.resize(got);
+    return out;
+  }
+  void series_stop() { check(sim_series_stop(h_), "sim_series_stop"); }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;

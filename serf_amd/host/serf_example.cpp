@@ -19,6 +19,7 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> trk = cl.track_add({
         serf::Cluster::member_tracker(11, 1u << SIM_STATUS_FAILED, 1u << SIM_SWIM_SUSPECT | 1u << SIM_SWIM_DEAD, 0, /*start=*/2),
         serf::Cluster::member_tracker(11, 1u << SIM_STATUS_FAILED, 0, 0, /*start=*/2)});
+    cl.series_start(/*first_tick=*/0, /*period=*/100, /*capacity=*/64);  // cluster gauges behind every 100th tick, read once at the end
     uint32_t rounds = 0;
     while (cl.convergence(SIM_K_EVENT, 42, 1) < 0.99 && rounds < 200) { cl.step(); ++rounds; }
     printf("user event reached 99%% of %u nodes after %u rounds\n", n, rounds);
@@ -39,6 +40,11 @@ int main(int argc, char** argv) {
     printf("crash of node 11 at tick 2: first suspicion at tick %u, declared failed by 99%% at tick %u, by all at tick %u\n",
            tr[0].first, tr[1].p99, tr[1].all);
     if (tr[0].first == SIM_TRACK_NEVER || tr[1].p99 == SIM_TRACK_NEVER || tr[0].first > tr[1].p99) return 1;
+    for (const sim_series_sample& sm : cl.series_read())
+      printf("  after tick %llu: %llu running, queue entries %llu/%llu/%llu/%llu, deepest queue %llu, %llu timers, %llu records in flight\n",
+             (unsigned long long)sm.w[0] - 1, (unsigned long long)sm.w[1], (unsigned long long)sm.w[6], (unsigned long long)sm.w[7],
+             (unsigned long long)sm.w[8], (unsigned long long)sm.w[9], (unsigned long long)sm.w[18], (unsigned long long)sm.w[27],
+             (unsigned long long)(sm.w[41] + sm.w[42] + sm.w[43] + sm.w[44] + sm.w[45] + sm.w[46] + sm.w[47]));
     for (const serf::Event& e : cl.drain_events())
       printf("  tick %u observer %u event %u key %u ltime %llu\n", e.tick, e.observer, e.type, e.key, (unsigned long long)e.ltime);
     return st.failed == 1 && st.left == 1 ? 0 : 1;

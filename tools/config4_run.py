@@ -20,7 +20,13 @@ The run of profiles/r07_config4_tracker.json (zero drops at 2 Mi nodes): --rando
 --reconnect-interval 150 --gossip-to-the-dead 150 --rumors 560 --burst 4 --crash-prob 0.1 --crash-cap 12.  Bursts have to lie further
 apart than an event needs to reach everybody: origins that have not seen the last burst give the next one the same Lamport time.
 
-Needs an MI355X.  Writes one JSON (default profiles/r03_config4_churn5_loss1_swim.json; --tracker: profiles/r07_config4_tracker.json)."""
+`--series PERIOD`: a DEVICE-RESIDENT TIME SERIES (include/serf_sim_series.h) of the same run — one sample of cluster gauges behind
+every PERIOD-th tick (queue entries by class, the queue-depth histogram, health scores, suspicion timers, clock spread, the records
+in flight by kind), read once at the end and written into the JSON under "series", one list per field.  It changes nothing else
+about the run.  The run of profiles/r08_config4_series.json: the r07 tracker run's options with --series 10.
+
+Needs an MI355X.  Writes one JSON (default profiles/r03_config4_churn5_loss1_swim.json; --tracker: profiles/r07_config4_tracker.json;
+--series: profiles/r08_config4_series.json)."""
 import argparse
 import json
 import os
@@ -34,6 +40,19 @@ sys.path.insert(0, ROOT)
 def hist(values):
     import numpy as np
     return {int(k): int(v) for k, v in zip(*np.unique(np.asarray(values, dtype=np.int64), return_counts=True))} if len(values) else {}
+
+
+def series_json(args, sim):
+    """The samples of the run's series, one list per field of _ffi.SERIES_DTYPE (vector fields: one list per sample)."""
+    taken, dropped = sim.series_count()
+    rec = sim.series_read()
+    out = {"period": args.series, "samples": int(taken), "dropped": int(dropped),
+           "what": "include/serf_sim_series.h: state after the tick `tick` - 1; per-node figures over RUNNING nodes; depth_bins = nodes with "
+                   "0, 1, 2-3, 4-7, 8-15, 16-31, 32-63, 64 queue entries; queued / records by class / kind; len64 in 16-byte units"}
+    for name in rec.dtype.names:
+        if name != "reserved":
+            out[name] = rec[name].tolist()
+    return out
 
 
 def run_tracker(args, sim, lib):
@@ -125,6 +144,7 @@ def run_tracker(args, sim, lib):
     harvest(sim.tick + args.max_rounds + args.down)
     fp = [r.as_dict() for r in sim.track_read(fp_ids)] if fp_ids else []
     cs = sim.cluster_stats()
+    series = series_json(args, sim) if args.series else None
 
     def rounds(name):
         return [r[name] - t for t, r in done_ev if r[name] != NEVER]
@@ -148,7 +168,9 @@ def run_tracker(args, sim, lib):
         "view_slots_recycled": int(cs["slots_recycled"]), "nodes_up_at_end": int(cs["up"]),
         "wall_s": dt, "member_ticks_per_s_incl_tracking": n * int(sim.tick) / dt,
     }
-    json.dump(out, open(args.out, "w"), indent=1)
+    if series:
+        out["series"] = series
+    json.dump(out, open(args.out, "w"), indent=None if series else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "sim_step_calls", "crashes", "events", "false_positives", "model_bound_drops", "ops_dropped_no_slot", "wall_s")}), "->", args.out)
     print(json.dumps({"rounds_to_99": out["rounds_to"]["99"], "detection": out["detection"]}))
 
@@ -184,10 +206,11 @@ def main():
     ap.add_argument("--crash-cap", type=int, default=10, help="--tracker: crashes inside one suspicion window (SIM_S = 16 timers per node, some are false suspicions)")
     ap.add_argument("--burst", type=int, default=4, help="--tracker: user events injected at once (they share a Lamport time, hence a ring bucket of SIM_C = 6 keys: more than 6 use up the overflow rows)")
     ap.add_argument("--fp-sample", type=int, default=64, help="--tracker: never-crashed nodes watched for false suspicions")
+    ap.add_argument("--series", type=int, default=0, metavar="PERIOD", help="sample the cluster gauges on the device behind every PERIOD-th tick (include/serf_sim_series.h) and put the series into the JSON")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
+        args.out = os.path.join(ROOT, "profiles", "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
 
     import numpy as np
     from serf_amd import _ffi
@@ -207,6 +230,8 @@ def main():
               **({"flags": _ffi.CF_BASELINE_JOINED | _ffi.CF_RANDOM_FANOUT} if args.random_fanout else {}),
               join_sync=True)   # Serf::join = memberlist.join: the re-joining node syncs with a peer (SIM_CF_JOIN_SYNC)
     sim = _ffi.Sim(lib, _ffi.make_config(n, **kw))
+    if args.series:
+        sim.series_start(0, args.series, min(_ffi.SERIES_MAX_SAMPLES, 1 << 16))
     if args.tracker:
         return run_tracker(args, sim, lib)
     rng = np.random.default_rng(5)
@@ -262,7 +287,7 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample")},
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series")},
         "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
@@ -285,7 +310,9 @@ def main():
                                 "what": "hipMemGetInfo at the end of the run: this handle's arrays (views, rings, packets, rows) and the runtime's own"}
     except Exception:
         pass
-    json.dump(out, open(args.out, "w"), indent=1)
+    if args.series:
+        out["series"] = series_json(args, sim)
+    json.dump(out, open(args.out, "w"), indent=None if args.series else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "churn_events", "rounds_to_99", "model_bound_drops", "ops_dropped_no_slot", "failure_detector", "wall_s")}), "->", args.out)
 
 
