@@ -134,6 +134,30 @@ SERIES_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("state", "<u8", (
 assert SERIES_DTYPE.itemsize == 8 * SERIES_WORDS
 
 
+# include/serf_sim_census.h: membership census (per subject, how the running nodes' views of it agree).  The third extension:
+# a version of its own, bound only when the loaded library exports it
+CENSUS_SYMBOLS = ("census_start", "census_count", "census_read", "census_stop", "census_now", "census_version")
+CENSUS_WORDS, CENSUS_MAX_SAMPLES = 16, 1 << 20
+# a subject's record and a sample's header as numpy records: the tables of include/serf_sim_census.h, 16 little-endian 64-bit
+# words each ("id" = subject | slot << 32: subject_of() / slot_of() below take it apart)
+CENSUS_SUBJECT_DTYPE = np.dtype([("id", "<u8"), ("running", "<u8"), ("status", "<u8", (5,)), ("swim", "<u8", (4,)),
+                                 ("intents", "<u8"), ("ltime_min", "<u8"), ("ltime_max", "<u8"), ("inc_min", "<u8"),
+                                 ("inc_max", "<u8")])
+CENSUS_HEADER_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("subjects", "<u8"), ("stored", "<u8"), ("settled", "<u8"),
+                                ("false_failed", "<u8"), ("false_failed_pairs", "<u8"), ("suspected_running", "<u8"),
+                                ("suspected_running_pairs", "<u8"), ("stopped_alive", "<u8"), ("stopped_alive_pairs", "<u8"),
+                                ("detected", "<u8"), ("reserved", "<u8", (4,))])
+assert CENSUS_SUBJECT_DTYPE.itemsize == CENSUS_HEADER_DTYPE.itemsize == 8 * CENSUS_WORDS
+
+
+def census_split(words, max_subjects):
+    """[samples * (1 + max_subjects) * 16] words -> (headers[samples], records[samples][max_subjects])."""
+    a = np.ascontiguousarray(np.asarray(words, np.uint64)).reshape(-1, 1 + max_subjects, CENSUS_WORDS)
+    hdr = np.ascontiguousarray(a[:, 0, :]).view(CENSUS_HEADER_DTYPE).reshape(-1)
+    rec = np.ascontiguousarray(a[:, 1:, :]).view(CENSUS_SUBJECT_DTYPE).reshape(-1, max_subjects)
+    return hdr, rec
+
+
 class Tracker(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32), ("min_inc", C.c_uint32),
                 ("ltime", C.c_uint64), ("start_tick", C.c_uint32), ("max_age", C.c_uint32)]
@@ -299,6 +323,20 @@ class SimLib:
                 fn = getattr(self.dll, prefix + name)
                 fn.restype, fn.argtypes = series[name]
                 self.f[name] = fn
+        census = {
+            "census_start": (C.c_int, [H, u32, u32, u32, u32]),
+            "census_count": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
+            "census_read": (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)]),
+            "census_stop": (C.c_int, [H]),
+            "census_now": (C.c_int, [H, vp, vp, u32, C.POINTER(u32)]),
+            "census_version": (u32, []),
+        }
+        self.has_census = all(hasattr(self.dll, prefix + name) for name in CENSUS_SYMBOLS)
+        if self.has_census:
+            for name in CENSUS_SYMBOLS:
+                fn = getattr(self.dll, prefix + name)
+                fn.restype, fn.argtypes = census[name]
+                self.f[name] = fn
 
     def backend_name(self):
         return self.f["backend_name"]().decode()
@@ -326,6 +364,10 @@ class SimLib:
     def series_version(self):
         """SIM_SERIES_VERSION of include/serf_sim_series.h, or None when the library has no series."""
         return self.f["series_version"]() if self.has_series else None
+
+    def census_version(self):
+        """SIM_CENSUS_VERSION of include/serf_sim_census.h, or None when the library has no census."""
+        return self.f["census_version"]() if self.has_census else None
 
 
 class Sim:
@@ -563,6 +605,52 @@ class Sim:
     def series_stop(self):
         """Ends the series and frees its buffers (the samples are gone)."""
         self._ck(self._series_fn("series_stop")(self.h), "sim_series_stop")
+
+    # ---- membership census (include/serf_sim_census.h) ----
+    def _census_fn(self, name):
+        if not self.lib.has_census:
+            raise NotImplementedError(f"{self.lib.path} exports no sim_census_* (include/serf_sim_census.h)")
+        return self.lib.f[name]
+
+    def census_start(self, first_tick=0, period=1, capacity=1 << 12, max_subjects=64):
+        """Starts a census: behind every tick t >= first_tick with (t - first_tick) % period == 0, until `capacity` samples
+        are held (a first_tick that has passed means "now"); a sample keeps the records of the first max_subjects subjects
+        in slot order, its header covers all of them."""
+        self._ck(self._census_fn("census_start")(self.h, first_tick, period, capacity, max_subjects), "sim_census_start")
+        self._census_max = max_subjects
+
+    def census_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        t, d = C.c_uint32(), C.c_uint32()
+        self._ck(self._census_fn("census_count")(self.h, C.byref(t), C.byref(d)), "sim_census_count")
+        return t.value, d.value
+
+    def census_read(self, first=0, n=None):
+        """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as (headers, records): numpy
+        arrays of CENSUS_HEADER_DTYPE [n] and CENSUS_SUBJECT_DTYPE [n][max_subjects] (a sample's records beyond
+        headers["stored"] are zero); waits for the handle's stream."""
+        fn = self._census_fn("census_read")
+        if n is None:
+            n = max(0, self.census_count()[0] - first)
+        ms = getattr(self, "_census_max", 1)
+        out = np.zeros(max(1, n) * (1 + ms) * CENSUS_WORDS, np.uint64)
+        got = C.c_uint32()
+        self._ck(fn(self.h, first, n, out.ctypes.data, out.size, C.byref(got)), "sim_census_read")
+        return census_split(out[:got.value * (1 + ms) * CENSUS_WORDS], ms)
+
+    def census_stop(self):
+        """Ends the census and frees its buffers (the samples are gone)."""
+        self._ck(self._census_fn("census_stop")(self.h), "sim_census_stop")
+
+    def census_now(self, cap=64):
+        """One census of the state the handle is in now, with or without a running one: (header, records[min(subjects,
+        cap)]); waits for the handle's stream.  The bulk counterpart of members()."""
+        fn = self._census_fn("census_now")
+        hdr = np.zeros(1, CENSUS_HEADER_DTYPE)
+        rec = np.zeros(max(1, cap), CENSUS_SUBJECT_DTYPE)
+        got = C.c_uint32()
+        self._ck(fn(self.h, hdr.ctypes.data, rec.ctypes.data, cap, C.byref(got)), "sim_census_now")
+        return hdr[0], rec[:got.value]
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

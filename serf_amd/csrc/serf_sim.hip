@@ -78,3 +78,4 @@ extern "C" {
 
 #include "serf_sim_track.inc"  // include/serf_sim_track.h: its kernels, its host part, an extern "C" block of its own
 #include "serf_sim_series.inc"  // include/serf_sim_series.h: likewise
+#include "serf_sim_census.inc"  // include/serf_sim_census.h: likewise

@@ -20,6 +20,7 @@ int sim_destroy(sim_handle* h) {
   if (h->xstream) (void)hipStreamSynchronize(h->xstream);
   if (h->trk) track_destroy(h);
   if (h->ser) series_destroy(h);
+  if (h->cen) census_destroy(h);
   if (h->xcomm) (void)ncclCommDestroy(h->xcomm);
   if (h->xstream) (void)hipStreamDestroy(h->xstream);
   if (h->xev_go) (void)hipEventDestroy(h->xev_go);
@@ -1229,7 +1230,8 @@ int sim_step_end(sim_handle* h) {
     h->sreq_tick[t % 3] = t;
   }
   if (h->trk) { if (int rc = track_step_end(h)) return rc; }  // registered trackers: the tick's evaluation follows it on the stream
-  if (h->ser) return series_step_end(h);  // a running series: the tick's sample, when one is due, likewise
+  if (h->ser) { if (int rc = series_step_end(h)) return rc; }  // a running series: the tick's sample, when one is due, likewise
+  if (h->cen) return census_step_end(h);  // a running census: likewise
   return SIM_OK;
 }
 // the list of one finished tick out of its buffer (sorted by prober); marks it read

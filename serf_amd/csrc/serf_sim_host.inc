@@ -139,6 +139,7 @@ struct sim_handle {
   u32* deep_seen;  // pinned: the longest deep list any launch has had (deep_queue_kernel keeps it; sizes that kernel's grid)
   struct TrackState* trk = nullptr;  // device-resident trackers (serf_sim_track.inc); null until the first sim_track_add
   struct SeriesState* ser = nullptr;  // device-resident time series (serf_sim_series.inc); null unless one is running
+  struct CensusState* cen = nullptr;  // membership census (serf_sim_census.inc); null unless one is running
 };
 // serf_sim_track.inc: the hooks of sim_step_end / sim_destroy (called only when h->trk)
 static int track_step_end(sim_handle* h);
@@ -146,6 +147,9 @@ static void track_destroy(sim_handle* h);
 // serf_sim_series.inc: likewise (called only when h->ser)
 static int series_step_end(sim_handle* h);
 static void series_destroy(sim_handle* h);
+// serf_sim_census.inc: likewise (called only when h->cen)
+static int census_step_end(sim_handle* h);
+static void census_destroy(sim_handle* h);
 
 #define HCHECK(x)                                                                        \
   do {                                                                                   \

@@ -10,6 +10,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <iterator>
 #include <stdexcept>
@@ -20,6 +21,7 @@
 #include "../../include/serf_sim.h"
 #include "../../include/serf_sim_track.h"
 #include "../../include/serf_sim_series.h"
+#include "../../include/serf_sim_census.h"
 #include "wire.hpp"
 
 namespace serf {
@@ -234,6 +236,46 @@ class Cluster {
     return out;
   }
   void series_stop() { check(sim_series_stop(h_), "sim_series_stop"); }
+  // membership census (include/serf_sim_census.h): behind every period-th tick one record per subject that owns a view slot — how
+  // many running nodes hold it Alive / Leaving / Left / Failed, Suspect / Dead, at which Lamport times and incarnations — and a
+  // header of cluster-wide figures (settled subjects, false positives, undetected failures).  HIP library only.
+  struct CensusSample {
+    sim_census_header header;
+    std::vector<sim_census_subject> subjects;  // header.w[3] of them, in slot order
+  };
+  void census_start(uint32_t first_tick = 0, uint32_t period = 1, uint32_t capacity = 1u << 12, uint32_t max_subjects = 64) {
+    check(sim_census_start(h_, first_tick, period, capacity, max_subjects), "sim_census_start");
+    census_max_ = max_subjects;
+  }
+  std::pair<uint32_t, uint32_t> census_count() const {  // (samples taken, dropped with the buffer full); waits for nothing
+    uint32_t t = 0, d = 0;
+    check(sim_census_count(h_, &t, &d), "sim_census_count");
+    return {t, d};
+  }
+  std::vector<CensusSample> census_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    if (n == 0xFFFFFFFFu) { const uint32_t t = census_count().first; n = t > first ? t - first : 0; }
+    const size_t stride = ((size_t)census_max_ + 1) * SIM_CENSUS_WORDS;
+    std::vector<uint64_t> words((n ? n : 1) * stride);
+    uint32_t got = 0;
+    check(sim_census_read(h_, first, n, words.data(), words.size(), &got), "sim_census_read");
+    std::vector<CensusSample> out(got);
+    for (uint32_t i = 0; i < got; ++i) {
+      const uint64_t* w = words.data() + i * stride;
+      std::memcpy(&out[i].header, w, sizeof(sim_census_header));
+      out[i].subjects.resize((size_t)out[i].header.w[3]);
+      if (!out[i].subjects.empty()) std::memcpy(out[i].subjects.data(), w + SIM_CENSUS_WORDS, out[i].subjects.size() * sizeof(sim_census_subject));
+    }
+    return out;
+  }
+  void census_stop() { check(sim_census_stop(h_), "sim_census_stop"); }
+  CensusSample census_now(uint32_t cap = 64) {  // the state the handle is in now, with or without a running census
+    CensusSample s;
+    s.subjects.resize(cap ? cap : 1);
+    uint32_t got = 0;
+    check(sim_census_now(h_, &s.header, s.subjects.data(), cap, &got), "sim_census_now");
+    s.subjects.resize(got);
+    return s;
+  }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;
@@ -248,6 +290,7 @@ class Cluster {
  private:
   sim_handle* h_ = nullptr;
   uint32_t n_;
+  uint32_t census_max_ = 1;  // max_subjects of the running census: the stride of its samples
 };
 
 inline std::vector<Member> Serf::members() const {

@@ -25,8 +25,14 @@ every PERIOD-th tick (queue entries by class, the queue-depth histogram, health 
 in flight by kind), read once at the end and written into the JSON under "series", one list per field.  It changes nothing else
 about the run.  The run of profiles/r08_config4_series.json: the r07 tracker run's options with --series 10.
 
+`--census PERIOD`: a MEMBERSHIP CENSUS (include/serf_sim_census.h) of the same run — behind every PERIOD-th tick the views of every
+subject that owns a view slot are counted on the device; the headers' curves (subjects, settled subjects, running subjects held
+Failed / Suspect-or-Dead and by how many, stopped subjects still held Alive, stopped subjects everybody knows gone) go into the JSON
+under "census", one list per field, with the subjects' records of the run's last tick.  Like --series it changes nothing else about
+the run and goes with either kind of run.  The run of profiles/r09_config4_census.json: see profiles/r09_census.md.
+
 Needs an MI355X.  Writes one JSON (default profiles/r03_config4_churn5_loss1_swim.json; --tracker: profiles/r07_config4_tracker.json;
---series: profiles/r08_config4_series.json)."""
+--series: profiles/r08_config4_series.json; --census: profiles/r09_config4_census.json)."""
 import argparse
 import json
 import os
@@ -52,6 +58,27 @@ def series_json(args, sim):
     for name in rec.dtype.names:
         if name != "reserved":
             out[name] = rec[name].tolist()
+    return out
+
+
+def census_json(args, sim):
+    """The headers of the run's census, one list per field of _ffi.CENSUS_HEADER_DTYPE, and the records of the state at the end."""
+    taken, dropped = sim.census_count()
+    hdr, _ = sim.census_read()
+    out = {"period": args.census, "samples": int(taken), "dropped": int(dropped),
+           "what": "include/serf_sim_census.h: state after the tick `tick` - 1; subjects = nodes that own a view slot, observers = running "
+                   "nodes; settled = subjects every observer holds the same entry of; false_failed / suspected_running = RUNNING subjects "
+                   "somebody holds Failed / Suspect or Dead (*_pairs: how many observers do); stopped_alive = STOPPED subjects somebody "
+                   "still holds Alive; detected = stopped subjects every observer holds Failed or Left"}
+    for name in hdr.dtype.names:
+        if name not in ("reserved", "stored"):
+            out[name] = hdr[name].tolist()
+    sub = [int(x) for x in hdr["subjects"]]
+    out["settled_share"] = [round(int(s) / n, 4) if n else None for s, n in zip(hdr["settled"], sub)]
+    _, rec = sim.census_now(64)
+    out["at_end"] = [{"subject": int(r["id"]) & 0xFFFFFFFF, "slot": int(r["id"]) >> 32, "running": int(r["running"]),
+                      "status": r["status"].tolist(), "swim": r["swim"].tolist(), "intents": int(r["intents"]),
+                      "ltime": [int(r["ltime_min"]), int(r["ltime_max"])], "inc": [int(r["inc_min"]), int(r["inc_max"])]} for r in rec]
     return out
 
 
@@ -145,6 +172,7 @@ def run_tracker(args, sim, lib):
     fp = [r.as_dict() for r in sim.track_read(fp_ids)] if fp_ids else []
     cs = sim.cluster_stats()
     series = series_json(args, sim) if args.series else None
+    census = census_json(args, sim) if args.census else None
 
     def rounds(name):
         return [r[name] - t for t, r in done_ev if r[name] != NEVER]
@@ -170,7 +198,9 @@ def run_tracker(args, sim, lib):
     }
     if series:
         out["series"] = series
-    json.dump(out, open(args.out, "w"), indent=None if series else 1)
+    if census:
+        out["census"] = census
+    json.dump(out, open(args.out, "w"), indent=None if series or census else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "sim_step_calls", "crashes", "events", "false_positives", "model_bound_drops", "ops_dropped_no_slot", "wall_s")}), "->", args.out)
     print(json.dumps({"rounds_to_99": out["rounds_to"]["99"], "detection": out["detection"]}))
 
@@ -207,10 +237,11 @@ def main():
     ap.add_argument("--burst", type=int, default=4, help="--tracker: user events injected at once (they share a Lamport time, hence a ring bucket of SIM_C = 6 keys: more than 6 use up the overflow rows)")
     ap.add_argument("--fp-sample", type=int, default=64, help="--tracker: never-crashed nodes watched for false suspicions")
     ap.add_argument("--series", type=int, default=0, metavar="PERIOD", help="sample the cluster gauges on the device behind every PERIOD-th tick (include/serf_sim_series.h) and put the series into the JSON")
+    ap.add_argument("--census", type=int, default=0, metavar="PERIOD", help="count the views of every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_census.h) and put the agreement curves into the JSON")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
+        args.out = os.path.join(ROOT, "profiles", "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
 
     import numpy as np
     from serf_amd import _ffi
@@ -232,6 +263,8 @@ def main():
     sim = _ffi.Sim(lib, _ffi.make_config(n, **kw))
     if args.series:
         sim.series_start(0, args.series, min(_ffi.SERIES_MAX_SAMPLES, 1 << 16))
+    if args.census:
+        sim.census_start(0, args.census, min(_ffi.CENSUS_MAX_SAMPLES, 1 << 16), 1)   # (the headers' curves: one record a sample is the least)
     if args.tracker:
         return run_tracker(args, sim, lib)
     rng = np.random.default_rng(5)
@@ -287,7 +320,7 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series")},
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census")},
         "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
@@ -312,7 +345,9 @@ def main():
         pass
     if args.series:
         out["series"] = series_json(args, sim)
-    json.dump(out, open(args.out, "w"), indent=None if args.series else 1)
+    if args.census:
+        out["census"] = census_json(args, sim)
+    json.dump(out, open(args.out, "w"), indent=None if args.series or args.census else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "churn_events", "rounds_to_99", "model_bound_drops", "ops_dropped_no_slot", "failure_detector", "wall_s")}), "->", args.out)
 
 
