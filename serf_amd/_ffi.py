@@ -533,37 +533,45 @@ class Sim:
         self._ck(self.lib.f["convergence_many"](self.h, n, kinds, keys, lts, seen, C.byref(up)), "sim_convergence_many")
         return [int(x) for x in seen[:n]], up.value
 
+    # ---- the extensions: trackers, series, census (include/serf_sim_<group>.h; the oracle has none of them) ----
+    def _ext_fn(self, group, name):
+        """sim_<group>_<name> of a library that exports the group."""
+        if not getattr(self.lib, "has_trackers" if group == "track" else "has_" + group):
+            raise NotImplementedError(f"{self.lib.path} exports no sim_{group}_* (include/serf_sim_{group}.h)")
+        return self.lib.f[f"{group}_{name}"]
+
+    def _sample_count(self, group):
+        t, d = C.c_uint32(), C.c_uint32()
+        self._ck(self._ext_fn(group, "count")(self.h, C.byref(t), C.byref(d)), f"sim_{group}_count")
+        return t.value, d.value
+
     # ---- device-resident trackers (include/serf_sim_track.h) ----
-    def _track_fn(self, name):
-        if not self.lib.has_trackers:
-            raise NotImplementedError(f"{self.lib.path} exports no sim_track_* (include/serf_sim_track.h)")
-        return self.lib.f[name]
 
     def track_add(self, trackers):
         """Registers a list of Tracker; returns their ids (stable until track_remove)."""
         n = len(trackers)
         arr = (Tracker * max(1, n))(*trackers)
         ids = (C.c_uint32 * max(1, n))()
-        self._ck(self._track_fn("track_add")(self.h, arr, n, ids), "sim_track_add")
+        self._ck(self._ext_fn("track", "add")(self.h, arr, n, ids), "sim_track_add")
         return list(ids[:n])
 
     def track_remove(self, ids):
         ids = list(ids)
         arr = (C.c_uint32 * max(1, len(ids)))(*ids)
-        self._ck(self._track_fn("track_remove")(self.h, arr, len(ids)), "sim_track_remove")
+        self._ck(self._ext_fn("track", "remove")(self.h, arr, len(ids)), "sim_track_remove")
 
     def track_read(self, ids):
         """[TrackResult] of the named trackers; waits for the handle's stream."""
         ids = list(ids)
         arr = (C.c_uint32 * max(1, len(ids)))(*ids)
         out = (TrackResult * max(1, len(ids)))()
-        self._ck(self._track_fn("track_read")(self.h, arr, len(ids), out), "sim_track_read")
+        self._ck(self._ext_fn("track", "read")(self.h, arr, len(ids), out), "sim_track_read")
         return list(out[:len(ids)])
 
     def track_active(self):
         """(registered, of which not retired)."""
         r, a = C.c_uint32(), C.c_uint32()
-        self._ck(self._track_fn("track_active")(self.h, C.byref(r), C.byref(a)), "sim_track_active")
+        self._ck(self._ext_fn("track", "active")(self.h, C.byref(r), C.byref(a)), "sim_track_active")
         return r.value, a.value
 
     def track_rumour(self, kind, key, ltime, start=0, max_age=0):
@@ -576,21 +584,14 @@ class Sim:
         return self.track_add([member_tracker(subject, status_mask, swim_mask, min_inc, start, max_age)])[0]
 
     # ---- device-resident time series (include/serf_sim_series.h) ----
-    def _series_fn(self, name):
-        if not self.lib.has_series:
-            raise NotImplementedError(f"{self.lib.path} exports no sim_series_* (include/serf_sim_series.h)")
-        return self.lib.f[name]
-
     def series_start(self, first_tick=0, period=1, capacity=1 << 16):
         """Starts sampling: behind every tick t >= first_tick with (t - first_tick) % period == 0, until `capacity` samples
         are held (a first_tick that has passed means "now")."""
-        self._ck(self._series_fn("series_start")(self.h, first_tick, period, capacity), "sim_series_start")
+        self._ck(self._ext_fn("series", "start")(self.h, first_tick, period, capacity), "sim_series_start")
 
     def series_count(self):
         """(samples taken, samples dropped because the buffer was full); waits for nothing."""
-        t, d = C.c_uint32(), C.c_uint32()
-        self._ck(self._series_fn("series_count")(self.h, C.byref(t), C.byref(d)), "sim_series_count")
-        return t.value, d.value
+        return self._sample_count("series")
 
     def series_read(self, first=0, n=None):
         """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as a numpy array of SERIES_DTYPE;
@@ -599,37 +600,30 @@ class Sim:
             n = max(0, self.series_count()[0] - first)
         out = np.zeros(max(1, n), SERIES_DTYPE)
         got = C.c_uint32()
-        self._ck(self._series_fn("series_read")(self.h, first, n, out.ctypes.data, C.byref(got)), "sim_series_read")
+        self._ck(self._ext_fn("series", "read")(self.h, first, n, out.ctypes.data, C.byref(got)), "sim_series_read")
         return out[:got.value]
 
     def series_stop(self):
         """Ends the series and frees its buffers (the samples are gone)."""
-        self._ck(self._series_fn("series_stop")(self.h), "sim_series_stop")
+        self._ck(self._ext_fn("series", "stop")(self.h), "sim_series_stop")
 
     # ---- membership census (include/serf_sim_census.h) ----
-    def _census_fn(self, name):
-        if not self.lib.has_census:
-            raise NotImplementedError(f"{self.lib.path} exports no sim_census_* (include/serf_sim_census.h)")
-        return self.lib.f[name]
-
     def census_start(self, first_tick=0, period=1, capacity=1 << 12, max_subjects=64):
         """Starts a census: behind every tick t >= first_tick with (t - first_tick) % period == 0, until `capacity` samples
         are held (a first_tick that has passed means "now"); a sample keeps the records of the first max_subjects subjects
         in slot order, its header covers all of them."""
-        self._ck(self._census_fn("census_start")(self.h, first_tick, period, capacity, max_subjects), "sim_census_start")
+        self._ck(self._ext_fn("census", "start")(self.h, first_tick, period, capacity, max_subjects), "sim_census_start")
         self._census_max = max_subjects
 
     def census_count(self):
         """(samples taken, samples dropped because the buffer was full); waits for nothing."""
-        t, d = C.c_uint32(), C.c_uint32()
-        self._ck(self._census_fn("census_count")(self.h, C.byref(t), C.byref(d)), "sim_census_count")
-        return t.value, d.value
+        return self._sample_count("census")
 
     def census_read(self, first=0, n=None):
         """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as (headers, records): numpy
         arrays of CENSUS_HEADER_DTYPE [n] and CENSUS_SUBJECT_DTYPE [n][max_subjects] (a sample's records beyond
         headers["stored"] are zero); waits for the handle's stream."""
-        fn = self._census_fn("census_read")
+        fn = self._ext_fn("census", "read")
         if n is None:
             n = max(0, self.census_count()[0] - first)
         ms = getattr(self, "_census_max", 1)
@@ -640,12 +634,12 @@ class Sim:
 
     def census_stop(self):
         """Ends the census and frees its buffers (the samples are gone)."""
-        self._ck(self._census_fn("census_stop")(self.h), "sim_census_stop")
+        self._ck(self._ext_fn("census", "stop")(self.h), "sim_census_stop")
 
     def census_now(self, cap=64):
         """One census of the state the handle is in now, with or without a running one: (header, records[min(subjects,
         cap)]); waits for the handle's stream.  The bulk counterpart of members()."""
-        fn = self._census_fn("census_now")
+        fn = self._ext_fn("census", "now")
         hdr = np.zeros(1, CENSUS_HEADER_DTYPE)
         rec = np.zeros(max(1, cap), CENSUS_SUBJECT_DTYPE)
         got = C.c_uint32()

@@ -59,13 +59,14 @@ typedef uint64_t u64;
 // every suspicion timer can fire (dead) and the probe can fail (suspect): Dev::npend = fanout * pkt_records + SIM_S + 1
 
 
-// One translation unit, ten files (r5: the 5 700-line file, split where its sections ended).  It stays ONE unit on purpose: the
+// One translation unit, eleven files (r5: the 5 700-line file, split where its sections ended).  It stays ONE unit on purpose: the
 // handlers are force-inlined into the tick kernel across these files — separate device translation units would need relocatable
 // device code, which changes the code the compiler generates for the hot kernel — and the host side launches the kernel
 // templates it instantiates.  bench.py stamps its PMC profiles with the hash of the DEVICE files (state, handlers, tick).
 #include "serf_sim_state.inc"
 #include "serf_sim_handlers.inc"
 #include "serf_sim_tick.inc"
+#include "serf_sim_observe.inc"  // what the observers share (wave reductions, the fold of partial results, the rumour predicate)
 #include "serf_sim_kernels.inc"
 #include "serf_sim_host.inc"
 

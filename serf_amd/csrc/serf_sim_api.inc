@@ -1511,20 +1511,29 @@ static int conv_plane(sim_handle* h, u32 kind, u64 ltime) {
   if (kind == SIM_K_QUERY) return lazy_need(h, h->lz_q, (u64)d.X + (u64)(d.bq_mask ? (u32)ltime & d.bq_mask : (u32)(ltime % d.Bq)) + 1);
   return SIM_OK;
 }
+// one pass of convergence_many_kernel: dev[0 .. cs.n] zeroed, counted into, copied to r[0 .. cs.n]; returns with the stream idle
+static int conv_run(sim_handle* h, const ConvSet& cs, u64* dev, u64* r) {
+  const size_t bytes = (size_t)(cs.n + 1) * 8;
+  hipStream_t s = h->stream;
+  HCHECK(hipMemsetAsync(dev, 0, bytes, s));
+  convergence_many_kernel<<<grid_for(h->d.Nl), BLOCK, 0, s>>>(h->d, h->d_base, cs, dev);
+  HCHECK(hipMemcpyAsync(r, dev, bytes, hipMemcpyDeviceToHost, s));
+  HCHECK(hipStreamSynchronize(s));
+  return SIM_OK;
+}
 int sim_convergence(sim_handle* h, uint32_t kind, uint32_t key, uint64_t ltime, uint64_t* seen, uint64_t* up) {
   if (!h || !seen || !up) return SIM_EINVAL;
   Dev& d = h->d;
   if (kind == SIM_K_JOIN || kind == SIM_K_LEAVE) { if (key >= d.N) return SIM_EINVAL; }
   else if (kind != SIM_K_EVENT && kind != SIM_K_QUERY) return SIM_EINVAL;
-  hipStream_t s = h->stream;
   if (int lrc = conv_plane(h, kind, ltime)) return lrc;
-  HCHECK(hipMemsetAsync(h->d_scratch + 8, 0, 16, s));
-  convergence_kernel<<<grid_for(d.Nl), BLOCK, 0, s>>>(d, h->d_base, kind, key, ltime, h->d_scratch + 8);
+  ConvSet cs;
+  memset(&cs, 0, sizeof cs);
+  cs.n = 1; cs.kind[0] = kind; cs.key[0] = key; cs.ltime[0] = ltime;
   u64 r[2];
-  HCHECK(hipMemcpyAsync(r, h->d_scratch + 8, 16, hipMemcpyDeviceToHost, s));
-  HCHECK(hipStreamSynchronize(s));
-  *seen = r[0];
-  *up = r[1];
+  if (int rc = conv_run(h, cs, h->d_scratch + 8, r)) return rc;  // (the handle's own words: no allocation per call)
+  *up = r[0];
+  *seen = r[1];
   return SIM_OK;
 }
 
@@ -1600,18 +1609,12 @@ int sim_convergence_many(sim_handle* h, uint32_t n, const uint32_t* kinds, const
     cs.kind[i] = kinds[i]; cs.key[i] = keys[i]; cs.ltime[i] = ltimes[i];
     if (int lrc = conv_plane(h, kinds[i], ltimes[i])) return lrc;
   }
-  hipStream_t s = h->stream;
   u64* scr = nullptr;
   if (hipMalloc((void**)&scr, (SIM_CONV_MAX + 1) * 8) != hipSuccess) return SIM_ENOMEM;
   u64 r[SIM_CONV_MAX + 1];
-  hipError_t e = hipMemsetAsync(scr, 0, sizeof r, s);
-  if (e == hipSuccess) {
-    convergence_many_kernel<<<grid_for(d.Nl), BLOCK, 0, s>>>(d, h->d_base, cs, scr);
-    e = hipMemcpyAsync(r, scr, sizeof r, hipMemcpyDeviceToHost, s);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  const int rc = conv_run(h, cs, scr, r);
   (void)hipFree(scr);
-  HCHECK(e);
+  if (rc) return rc;
   *up = r[0];
   for (u32 i = 0; i < n; ++i) seen[i] = r[1 + i];
   return SIM_OK;

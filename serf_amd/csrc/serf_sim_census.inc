@@ -96,9 +96,9 @@ __global__ __launch_bounds__(BLOCK) void census_count_kernel(CenDevP p) {
 #pragma unroll
   for (u32 k = 0; k < 10; ++k) s[k >> 2] |= ((cnt >> (6u * k)) & 63ull) << (16u * (k & 3u));
 #pragma unroll
-  for (int k = 0; k < 3; ++k) s[k] = ser_wsum(s[k]);
-  ltmin = ser_wmin(ltmin); ltmax = ser_wmax(ltmax);
-  const u64 ilo = ser_wmin((u64)imin), ihi = ser_wmax((u64)imax);
+  for (int k = 0; k < 3; ++k) s[k] = wave_sum(s[k]);
+  ltmin = wave_min(ltmin); ltmax = wave_max(ltmax);
+  const u64 ilo = wave_min((u64)imin), ihi = wave_max((u64)imax);
   if ((threadIdx.x & 63) == 0) {
     u64* r = red[threadIdx.x >> 6];
     r[0] = s[0]; r[1] = s[1]; r[2] = s[2]; r[3] = ltmin; r[4] = ltmax; r[5] = ilo; r[6] = ihi;
@@ -128,6 +128,7 @@ __global__ __launch_bounds__(BLOCK) void census_fold_kernel(CenDevP p) {
   if (a >= p.bound) return;  // (whole waves)
   const u32 subj = p.subject_of[a];
   if (subj == NOSLOT) return;  // (the pack kernel asks subject_of too: rec[a] is not read)
+  // (fourteen rows in ONE pass, their loads in flight together: fold_row fourteen times is fourteen loops — six more VGPRs, a wave less per SIMD)
   u64 v[14];
 #pragma unroll
   for (u32 w = 0; w < 14; ++w) v[w] = (w == 10u || w == 12u) ? ~0ull : 0ull;
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(BLOCK) void census_fold_kernel(CenDevP p) {
     }
   }
 #pragma unroll
-  for (u32 w = 0; w < 14; ++w) v[w] = w < 10u ? ser_wsum(v[w]) : (w == 10u || w == 12u) ? ser_wmin(v[w]) : ser_wmax(v[w]);
+  for (u32 w = 0; w < 14; ++w) v[w] = w < 10u ? wave_sum(v[w]) : (w == 10u || w == 12u) ? wave_min(v[w]) : wave_max(v[w]);
   if (lane) return;
   u64* r = p.rec + (size_t)a * SIM_CENSUS_WORDS;
   const bool anyknown = (v[5] | v[6] | v[7] | v[8]) != 0;  // (the swim bins: the known observers)
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(BLOCK) void census_pack_kernel(CenDevP p) {
     __syncthreads();
     u32 c = 0;
     for (u32 a = threadIdx.x; a < p.bound; a += BLOCK) c += p.subject_of[a] != NOSLOT ? 1u : 0u;
-    c = (u32)ser_wsum(c);
+    c = (u32)wave_sum(c);
     if (!lane) atomicAdd(&hacc[0], (unsigned long long)c);  // (LDS)
     __syncthreads();
     const u32 stored = (u32)min((u64)hacc[0], (u64)p.maxsub);
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(BLOCK) void census_pack_kernel(CenDevP p) {
       if (w == nupw - 1u && (p.N & 31u)) x &= (1u << (p.N & 31u)) - 1u;
       c += (u32)__popc(x);
     }
-    c = (u32)ser_wsum(c);
+    c = (u32)wave_sum(c);
     if (!lane) atomicAdd(&hacc[CH_UP], (unsigned long long)c);
   }
   __syncthreads();
@@ -237,7 +238,7 @@ __global__ __launch_bounds__(BLOCK) void census_pack_kernel(CenDevP p) {
     const u64 v[8] = {hs[0], hs[1], hp[0], hs[3], hp[1], hs[5], hp[2], hs[7]};
 #pragma unroll
     for (u32 i = 0; i < 8; ++i) {
-      const u64 t = ser_wsum(v[i]);
+      const u64 t = wave_sum(v[i]);
       if (!lane && t) atomicAdd(&hacc[CH_SETTLED + i], (unsigned long long)t);
     }
   }
@@ -254,9 +255,8 @@ __global__ __launch_bounds__(BLOCK) void census_pack_kernel(CenDevP p) {
 struct CensusState {
   u64* d_part = nullptr;  // [A][SIM_CENSUS_WORDS][S]
   u64* d_rec = nullptr;   // [A][SIM_CENSUS_WORDS]
-  u64* d_buf = nullptr;   // [cap] samples of (1 + maxsub) * SIM_CENSUS_WORDS words
-  u64 first = 0;          // the first sampled tick
-  u32 period = 1, cap = 0, maxsub = 0, taken = 0, dropped = 0;
+  Sampler smp;            // samples of (1 + maxsub) * SIM_CENSUS_WORDS words
+  u32 maxsub = 0;
 };
 static inline u32 census_segments(const sim_handle* h) { return (h->d.Nl + CEN_SEG - 1u) / CEN_SEG; }
 static inline size_t census_stride(u32 maxsub) { return ((size_t)maxsub + 1u) * SIM_CENSUS_WORDS; }  // words of a sample
@@ -280,7 +280,7 @@ static void census_destroy(sim_handle* h) {
   if (!s) return;
   if (s->d_part) (void)hipFree(s->d_part);
   if (s->d_rec) (void)hipFree(s->d_rec);
-  if (s->d_buf) (void)hipFree(s->d_buf);
+  sampler_close(s->smp);
   delete s;
   h->cen = nullptr;
 }
@@ -305,16 +305,10 @@ static int census_launch(sim_handle* h, u64* part, u64* rec, u64* out, u32 maxsu
 // sim_step_end: tick h->tick - 1 has been enqueued; a sample of it follows it on the stream
 static int census_step_end(sim_handle* h) {
   CensusState* s = h->cen;
-  const u64 t = h->tick - 1;
-  if (t < s->first || (t - s->first) % s->period) return SIM_OK;
-  if (s->taken == s->cap) { s->dropped++; return SIM_OK; }
-  if (int rc = census_launch(h, s->d_part, s->d_rec, s->d_buf + (size_t)s->taken * census_stride(s->maxsub), s->maxsub)) return rc;
-  s->taken++;
-  return SIM_OK;
-}
-static int census_usable(const sim_handle* h) {
-  if (!h) return SIM_EINVAL;
-  if (h->d.sharded || h->in_tick) return SIM_ESTATE;
+  u64* slot = sampler_slot(h, s->smp);
+  if (!slot) return SIM_OK;
+  if (int rc = census_launch(h, s->d_part, s->d_rec, slot, s->maxsub)) return rc;
+  sampler_commit(s->smp);
   return SIM_OK;
 }
 
@@ -323,48 +317,37 @@ extern "C" {
 uint32_t sim_census_version(void) { return SIM_CENSUS_VERSION; }
 
 int sim_census_start(sim_handle* h, uint32_t first_tick, uint32_t period, uint32_t capacity, uint32_t max_subjects) {
-  if (int rc = census_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!period || !capacity || capacity > SIM_CENSUS_MAX_SAMPLES || !max_subjects) return SIM_EINVAL;
   if (h->cen) return SIM_ESTATE;
   CensusState* s = new CensusState();
+  h->cen = s;
+  s->maxsub = max_subjects;
   if (census_scratch(h, &s->d_part, &s->d_rec) != SIM_OK ||
-      hipMalloc((void**)&s->d_buf, (size_t)capacity * census_stride(max_subjects) * 8) != hipSuccess) {
+      sampler_open(h, s->smp, first_tick, period, capacity, census_stride(max_subjects)) != SIM_OK) {
     (void)hipGetLastError();
-    h->cen = s;
     census_destroy(h);
     return SIM_ENOMEM;
   }
-  s->first = std::max<u64>(first_tick, h->tick);
-  s->period = period;
-  s->cap = capacity;
-  s->maxsub = max_subjects;
-  h->cen = s;
   return SIM_OK;
 }
 
 int sim_census_count(const sim_handle* h, uint32_t* taken, uint32_t* dropped) {
-  if (int rc = census_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!taken || !dropped) return SIM_EINVAL;
-  *taken = h->cen ? h->cen->taken : 0u;
-  *dropped = h->cen ? h->cen->dropped : 0u;
+  sampler_count(h->cen ? &h->cen->smp : nullptr, taken, dropped);
   return SIM_OK;
 }
 
 int sim_census_read(sim_handle* h, uint32_t first, uint32_t n, uint64_t* out, size_t cap_words, uint32_t* n_out) {
-  if (int rc = census_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!out || !n_out) return SIM_EINVAL;
   if (!h->cen) return SIM_ESTATE;
-  const CensusState* s = h->cen;
-  const size_t stride = census_stride(s->maxsub);
-  if ((u64)first + n > s->taken || (size_t)n * stride > cap_words) return SIM_EINVAL;
-  HCHECK(hipStreamSynchronize(h->stream));
-  if (n) HCHECK(hipMemcpy(out, s->d_buf + (size_t)first * stride, (size_t)n * stride * 8, hipMemcpyDeviceToHost));
-  *n_out = n;
-  return SIM_OK;
+  return sampler_read(h, h->cen->smp, first, n, out, cap_words, n_out);
 }
 
 int sim_census_stop(sim_handle* h) {
-  if (int rc = census_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!h->cen) return SIM_ESTATE;
   HCHECK(hipStreamSynchronize(h->stream));  // (samples still enqueued write into the buffers)
   census_destroy(h);
@@ -372,7 +355,7 @@ int sim_census_stop(sim_handle* h) {
 }
 
 int sim_census_now(sim_handle* h, sim_census_header* hdr, sim_census_subject* recs, uint32_t cap, uint32_t* n) {
-  if (int rc = census_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!hdr || !n || (cap && !recs)) return SIM_EINVAL;
   const u32 maxsub = std::min(cap, h->d.A);  // (there are no more subjects than slots)
   u64 *part = nullptr, *rec = nullptr, *out = nullptr;

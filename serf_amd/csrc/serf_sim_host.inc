@@ -309,3 +309,55 @@ static int rings_need(sim_handle* h) {
   return rc ? rc : lazy_need(h, h->lz_q, h->d.X + h->q_hi + 2);
 }
 #define EV_CAP (1u << 20)
+
+// ---- what the observers share on the host (the device part: serf_sim_observe.inc; it stands here because it needs the handle) ----
+// trackers, series and census watch a handle that holds every node, between ticks
+static int observer_usable(const sim_handle* h) {
+  if (!h) return SIM_EINVAL;
+  if (h->d.sharded || h->in_tick) return SIM_ESTATE;
+  return SIM_OK;
+}
+// A device buffer of samples, one behind every period-th tick from `first` on until it is full.  The host knows every sampled tick in
+// advance: it passes a sample's place to the launches that write it and reads nothing back.
+struct Sampler {
+  u64* d_buf = nullptr;     // [cap] samples of stride_words words
+  size_t stride_words = 0;
+  u64 first = 0;            // the first sampled tick
+  u32 period = 1, cap = 0, taken = 0, dropped = 0;
+};
+static int sampler_open(const sim_handle* h, Sampler& S, u32 first_tick, u32 period, u32 capacity, size_t stride_words) {
+  if (hipMalloc((void**)&S.d_buf, (size_t)capacity * stride_words * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    S.d_buf = nullptr;
+    return SIM_ENOMEM;
+  }
+  S.stride_words = stride_words;
+  S.first = std::max<u64>(first_tick, h->tick);
+  S.period = period;
+  S.cap = capacity;
+  return SIM_OK;
+}
+// sim_step_end, tick h->tick - 1 enqueued: where its sample goes — null when none is due, or when the buffer is full (counted)
+static u64* sampler_slot(const sim_handle* h, Sampler& S) {
+  const u64 t = h->tick - 1;
+  if (t < S.first || (t - S.first) % S.period) return nullptr;
+  if (S.taken == S.cap) { S.dropped++; return nullptr; }
+  return S.d_buf + (size_t)S.taken * S.stride_words;
+}
+static inline void sampler_commit(Sampler& S) { S.taken++; }  // (behind launches that were enqueued without error)
+static void sampler_count(const Sampler* S, u32* taken, u32* dropped) {  // (null: nothing runs)
+  *taken = S ? S->taken : 0u;
+  *dropped = S ? S->dropped : 0u;
+}
+// samples first .. first + n - 1 into out[cap_words]; waits for the handle's stream
+static int sampler_read(sim_handle* h, const Sampler& S, u32 first, u32 n, void* out, size_t cap_words, u32* n_out) {
+  if ((u64)first + n > S.taken || (size_t)n * S.stride_words > cap_words) return SIM_EINVAL;
+  HCHECK(hipStreamSynchronize(h->stream));
+  if (n) HCHECK(hipMemcpy(out, S.d_buf + (size_t)first * S.stride_words, (size_t)n * S.stride_words * 8, hipMemcpyDeviceToHost));
+  *n_out = n;
+  return SIM_OK;
+}
+static void sampler_close(Sampler& S) {  // (the caller has waited for the samples still enqueued)
+  if (S.d_buf) (void)hipFree(S.d_buf);
+  S.d_buf = nullptr;
+}

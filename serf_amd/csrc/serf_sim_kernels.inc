@@ -1241,7 +1241,7 @@ __global__ void restore_queue_kernel(Dev d, const uint4* in /* [Nl][Q] canonical
 __device__ static inline u64 dig(u64 w, u64 idx) { return mix64(w ^ (idx * 0xD1342543DE82EF95ull)); }
 __device__ static inline void block_sum_add(u64 v, u64* out) {
   __shared__ u64 sm[BLOCK / 64];
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1352,30 +1352,7 @@ __global__ void members_kernel(Dev d, const uint4* base, u32 obs_l, uint8_t* st,
     lt[s] = known ? E_LTIME(e) : 0;
   }
 }
-__global__ void convergence_kernel(Dev d, const uint4* base, u32 kind, u32 key, u64 ltime, u64* out /*[2]*/) {
-  u64 seen = 0, upc = 0;
-  for (size_t l = blockIdx.x * (size_t)BLOCK + threadIdx.x; l < d.Nl; l += (size_t)gridDim.x * BLOCK) {
-    if (!(d.R1[l].z & SIM_RF_UP)) continue;
-    upc++;
-    if (kind == SIM_K_JOIN || kind == SIM_K_LEAVE) {
-      u32 a = d.slot_of[key];
-      uint4 e = a == NOSLOT ? base[(size_t)key * 2] : d.view[(size_t)a * d.Nl + l];
-      seen += ((e.w & SIM_VB_KNOWN) && E_LTIME(e) >= ltime);
-    } else {
-      const uint4* ring = kind == SIM_K_EVENT ? d.ering : d.qring;
-      u32 B = kind == SIM_K_EVENT ? d.Bev : d.Bq;
-      const uint4* p = ring + ((size_t)(ltime % B) * d.Nl + l);
-      const size_t tl = kind == SIM_K_EVENT ? d.etail : d.qtail;
-      uint4 b0 = p[0], b1 = p[tl];
-      bool hit = (b0.z == key) | (b0.w == key) | (b1.x == key) | (b1.y == key) | (b1.z == key) | (b1.w == key);
-      if (!hit && b1.w && key) hit = ovf_has(d, ring, tl, (u32)l, (u32)(ltime % B), key);  // a full bucket: its overflow rows
-      seen += hit;
-    }
-  }
-  block_sum_add(seen, out);
-  block_sum_add(upc, out + 1);
-}
-// the same for up to SIM_CONV_MAX rumours in one pass: out[0] = running nodes, out[1 + i] = those that have applied rumour i
+// up to SIM_CONV_MAX rumours in one pass (sim_convergence: one): out[0] = running nodes, out[1 + i] = those that have applied rumour i
 struct ConvSet { u32 n; u32 kind[SIM_CONV_MAX], key[SIM_CONV_MAX]; u64 ltime[SIM_CONV_MAX]; };
 __global__ void convergence_many_kernel(Dev d, const uint4* base, ConvSet cs, u64* out) {
   __shared__ u32 cnt[SIM_CONV_MAX + 1];
@@ -1395,19 +1372,11 @@ __global__ void convergence_many_kernel(Dev d, const uint4* base, ConvSet cs, u6
         if (kind == SIM_K_JOIN || kind == SIM_K_LEAVE) {
           u32 a = d.slot_of[key];
           uint4 e = a == NOSLOT ? base[(size_t)key * 2] : d.view[(size_t)a * d.Nl + l];
-          hit = (e.w & SIM_VB_KNOWN) && E_LTIME(e) >= ltime;
+          hit = view_applied(e, ltime);
         } else {
           const uint4* ring = kind == SIM_K_EVENT ? d.ering : d.qring;
-          u32 B = kind == SIM_K_EVENT ? d.Bev : d.Bq;
-          const uint4* p = ring + ((size_t)(ltime % B) * d.Nl + l);
-          uint4 b0 = p[0];
-          hit = (b0.z == key) | (b0.w == key);
-          if (!hit && b0.w) {  // the tail plane only when the head is full and does not hold the key
-            const size_t tl = kind == SIM_K_EVENT ? d.etail : d.qtail;
-            uint4 b1 = p[tl];
-            hit = (b1.x == key) | (b1.y == key) | (b1.z == key) | (b1.w == key);
-            if (!hit && b1.w && key) hit = ovf_has(d, ring, tl, (u32)l, (u32)(ltime % B), key);  // a full bucket: its overflow rows
-          }
+          const u32 idx = (u32)(ltime % (kind == SIM_K_EVENT ? d.Bev : d.Bq));
+          hit = bucket_holds(d, ring, kind == SIM_K_EVENT ? d.etail : d.qtail, idx, l, ring[(size_t)idx * d.Nl + l], key);
         }
       }
       u64 hm = __ballot(hit);
@@ -1463,13 +1432,10 @@ __global__ void cluster_stats_kernel(Dev d, const uint4* inbox, u64* part) {
         for (u32 p = 0; p < SIM_P; ++p) a[6] += SIM_META_KIND(pk_word(inbox[((size_t)k * d.Nl + l) * PK_U4 + 2], p)) != SIM_K_EMPTY;
   }
   __shared__ u64 sm[10][BLOCK / 64];
-  for (int i = 0; i < 9; ++i) {
-    u64 v = a[i];
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
+  for (int i = 0; i < 10; ++i) {
+    const u64 v = i == 9 ? wave_max(mx) : wave_sum(a[i]);
     if ((threadIdx.x & 63) == 0) sm[i][threadIdx.x >> 6] = v;
   }
-  for (int o = 32; o >= 1; o >>= 1) mx = max(mx, (u32)__shfl_down((int)mx, o, 64));
-  if ((threadIdx.x & 63) == 0) sm[9][threadIdx.x >> 6] = mx;
   __syncthreads();
   if (threadIdx.x < 10) {
     u64 t = 0;
@@ -1481,10 +1447,7 @@ __global__ void cluster_stats_fold(const u64* part, u32 nwg, u64* out) {  // one
   const u32 i = threadIdx.y;
   u64 t = 0;
   for (u32 w = threadIdx.x; w < nwg; w += 64u) t = i == 9 ? max(t, part[(size_t)w * 10 + i]) : t + part[(size_t)w * 10 + i];
-  for (int o = 32; o >= 1; o >>= 1) {
-    const u64 y = __shfl_down(t, o, 64);
-    t = i == 9 ? max(t, y) : t + y;
-  }
+  t = i == 9 ? wave_max(t) : wave_sum(t);
   if (threadIdx.x == 0) out[i] = t;
 }
 // single-word / single-entry updates of device tables with the value passed by value (no host buffer to outlive)

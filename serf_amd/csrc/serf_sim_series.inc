@@ -20,11 +20,11 @@ enum {
   SW_FAILED = 29, SW_LEFT = 30, SW_KMIN = 31, SW_KMAX = 32, SW_CLK = 33, SW_OVERFLOW = 39, SW_PKTS = 40, SW_KIND = 41, SW_LEN = 48,
   SW_USED = 49
 };
-// how a word's partial results combine: 0 sum, 1 min, 2 max
+// how a word's partial results combine
 __host__ __device__ static inline u32 ser_op(u32 w) {
-  if (w == SW_KMIN || w == SW_CLK || w == SW_CLK + 2 || w == SW_CLK + 4) return 1u;
-  if (w == SW_MAXDEPTH || w == SW_KMAX || w == SW_CLK + 1 || w == SW_CLK + 3 || w == SW_CLK + 5) return 2u;
-  return 0u;
+  if (w == SW_KMIN || w == SW_CLK || w == SW_CLK + 2 || w == SW_CLK + 4) return FOLD_MIN;
+  if (w == SW_MAXDEPTH || w == SW_KMAX || w == SW_CLK + 1 || w == SW_CLK + 3 || w == SW_CLK + 5) return FOLD_MAX;
+  return FOLD_SUM;
 }
 
 struct SerDevP {
@@ -36,22 +36,9 @@ struct SerDevP {
   u32 nslot;   // fan-out slots that carry packets: f (random fan-out), feff of the tick that sent them (bijection)
 };
 
-__device__ static inline u64 ser_wsum(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ static inline u64 ser_wmin(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) { const u64 y = __shfl_xor(v, o); v = y < v ? y : v; }
-  return v;
-}
-__device__ static inline u64 ser_wmax(u64 v) {
-  for (int o = 32; o > 0; o >>= 1) { const u64 y = __shfl_xor(v, o); v = y > v ? y : v; }
-  return v;
-}
-
 __global__ __launch_bounds__(BLOCK) void series_sample_kernel(Dev d, SerDevP p) {
   __shared__ u64 acc[SIM_SERIES_WORDS];
-  if (threadIdx.x < SIM_SERIES_WORDS) acc[threadIdx.x] = ser_op(threadIdx.x) == 1u ? ~0ull : 0ull;
+  if (threadIdx.x < SIM_SERIES_WORDS) acc[threadIdx.x] = ser_op(threadIdx.x) == FOLD_MIN ? ~0ull : 0ull;
   __syncthreads();
   // counts of nodes: a ballot per bin, kept per wave (the same value in every lane: scalar registers)
   u32 c_up = 0, c_tn = 0, c_state[4] = {0, 0, 0, 0}, c_bin[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c_aw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -171,7 +158,7 @@ __global__ __launch_bounds__(BLOCK) void series_sample_kernel(Dev d, SerDevP p) 
                       SW_KIND + 0, SW_KIND + 1, SW_KIND + 4, SW_KIND + 5};
 #pragma unroll
   for (int i = 0; i < 14; ++i) {
-    const u64 v = ser_wsum(s[i]);
+    const u64 v = wave_sum(s[i]);
     if (!lane0 || !v) continue;
     if (i < 10) atomicAdd((unsigned long long*)&acc[sw[i]], (unsigned long long)v);
     else {  // two kinds in one word: the second is two kinds further on
@@ -185,12 +172,12 @@ __global__ __launch_bounds__(BLOCK) void series_sample_kernel(Dev d, SerDevP p) 
     const u32 wmin[4] = {SW_KMIN, SW_CLK, SW_CLK + 2, SW_CLK + 4}, wmax[5] = {SW_KMAX, SW_CLK + 1, SW_CLK + 3, SW_CLK + 5, SW_MAXDEPTH};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const u64 v = ser_wmin(vmin[i]);
+      const u64 v = wave_min(vmin[i]);
       if (lane0) atomicMin((unsigned long long*)&acc[wmin[i]], (unsigned long long)v);
     }
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
-      const u64 v = ser_wmax(vmax[i]);
+      const u64 v = wave_max(vmax[i]);
       if (lane0) atomicMax((unsigned long long*)&acc[wmax[i]], (unsigned long long)v);
     }
   }
@@ -202,17 +189,10 @@ __global__ __launch_bounds__(BLOCK) void series_sample_kernel(Dev d, SerDevP p) 
 __global__ __launch_bounds__(BLOCK) void series_fold_kernel(SerDevP p) {
   const u32 w = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (w >= SIM_SERIES_WORDS) return;  // (whole waves)
-  const u32 op = ser_op(w);
-  u64 v = op == 1u ? ~0ull : 0ull;
+  u64 v = w == SW_TICK ? (u64)p.now : 0ull;
   if (w != SW_TICK && w < SW_USED) {
-    for (u32 g = lane; g < p.G; g += 64) {
-      const u64 y = p.part[(size_t)w * p.G + g];
-      v = op == 0u ? v + y : op == 1u ? (y < v ? y : v) : (y > v ? y : v);
-    }
-    v = op == 0u ? ser_wsum(v) : op == 1u ? ser_wmin(v) : ser_wmax(v);
-    if (op == 1u && v == ~0ull) v = 0;  // no node runs
-  } else {
-    v = w == SW_TICK ? (u64)p.now : 0ull;
+    v = fold_row(p.part + (size_t)w * p.G, p.G, ser_op(w));
+    if (ser_op(w) == FOLD_MIN && v == ~0ull) v = 0;  // no node runs
   }
   if (!lane) p.out[w] = v;
 }
@@ -220,29 +200,26 @@ __global__ __launch_bounds__(BLOCK) void series_fold_kernel(SerDevP p) {
 // ---- host ----
 struct SeriesState {
   u64* d_part = nullptr;  // [SIM_SERIES_WORDS][SER_GRID]
-  u64* d_buf = nullptr;   // [cap] samples
-  u64 first = 0;          // the first sampled tick
-  u32 period = 1, cap = 0, taken = 0, dropped = 0;
+  Sampler smp;            // samples of SIM_SERIES_WORDS words
 };
 
 static void series_destroy(sim_handle* h) {
   SeriesState* s = h->ser;
   if (!s) return;
   if (s->d_part) (void)hipFree(s->d_part);
-  if (s->d_buf) (void)hipFree(s->d_buf);
+  sampler_close(s->smp);
   delete s;
   h->ser = nullptr;
 }
 // sim_step_end: tick h->tick - 1 has been enqueued; a sample of it follows it on the stream
 static int series_step_end(sim_handle* h) {
   SeriesState* s = h->ser;
-  const u64 t = h->tick - 1;
-  if (t < s->first || (t - s->first) % s->period) return SIM_OK;
-  if (s->taken == s->cap) { s->dropped++; return SIM_OK; }
+  u64* slot = sampler_slot(h, s->smp);
+  if (!slot) return SIM_OK;
   const Dev& d = h->d;
   SerDevP p;
   p.part = s->d_part;
-  p.out = s->d_buf + (size_t)s->taken * SIM_SERIES_WORDS;
+  p.out = slot;
   p.G = (u32)std::min<size_t>(((size_t)d.Nl + BLOCK - 1) / BLOCK, SER_GRID);
   p.now = (u32)h->tick;
   p.cur = (u32)(h->tick & 1);
@@ -250,12 +227,7 @@ static int series_step_end(sim_handle* h) {
   series_sample_kernel<<<p.G, BLOCK, 0, h->stream>>>(d, p);
   series_fold_kernel<<<SIM_SERIES_WORDS / (BLOCK / 64), BLOCK, 0, h->stream>>>(p);
   HCHECK(hipGetLastError());
-  s->taken++;
-  return SIM_OK;
-}
-static int series_usable(const sim_handle* h) {
-  if (!h) return SIM_EINVAL;
-  if (h->d.sharded || h->in_tick) return SIM_ESTATE;
+  sampler_commit(s->smp);
   return SIM_OK;
 }
 
@@ -264,46 +236,36 @@ extern "C" {
 uint32_t sim_series_version(void) { return SIM_SERIES_VERSION; }
 
 int sim_series_start(sim_handle* h, uint32_t first_tick, uint32_t period, uint32_t capacity) {
-  if (int rc = series_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!period || !capacity || capacity > SIM_SERIES_MAX_SAMPLES) return SIM_EINVAL;
   if (h->ser) return SIM_ESTATE;
   SeriesState* s = new SeriesState();
+  h->ser = s;
   if (hipMalloc((void**)&s->d_part, (size_t)SIM_SERIES_WORDS * SER_GRID * 8) != hipSuccess ||
-      hipMalloc((void**)&s->d_buf, (size_t)capacity * sizeof(sim_series_sample)) != hipSuccess) {
+      sampler_open(h, s->smp, first_tick, period, capacity, SIM_SERIES_WORDS) != SIM_OK) {
     (void)hipGetLastError();
-    h->ser = s;
     series_destroy(h);
     return SIM_ENOMEM;
   }
-  s->first = std::max<u64>(first_tick, h->tick);
-  s->period = period;
-  s->cap = capacity;
-  h->ser = s;
   return SIM_OK;
 }
 
 int sim_series_count(const sim_handle* h, uint32_t* taken, uint32_t* dropped) {
-  if (int rc = series_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!taken || !dropped) return SIM_EINVAL;
-  *taken = h->ser ? h->ser->taken : 0u;
-  *dropped = h->ser ? h->ser->dropped : 0u;
+  sampler_count(h->ser ? &h->ser->smp : nullptr, taken, dropped);
   return SIM_OK;
 }
 
 int sim_series_read(sim_handle* h, uint32_t first, uint32_t n, sim_series_sample* out, uint32_t* n_out) {
-  if (int rc = series_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!out || !n_out) return SIM_EINVAL;
   if (!h->ser) return SIM_ESTATE;
-  const SeriesState* s = h->ser;
-  if ((u64)first + n > s->taken) return SIM_EINVAL;
-  HCHECK(hipStreamSynchronize(h->stream));
-  if (n) HCHECK(hipMemcpy(out, s->d_buf + (size_t)first * SIM_SERIES_WORDS, (size_t)n * sizeof(sim_series_sample), hipMemcpyDeviceToHost));
-  *n_out = n;
-  return SIM_OK;
+  return sampler_read(h, h->ser->smp, first, n, out, ~(size_t)0, n_out);
 }
 
 int sim_series_stop(sim_handle* h) {
-  if (int rc = series_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!h->ser) return SIM_ESTATE;
   HCHECK(hipStreamSynchronize(h->stream));  // (samples still enqueued write into the buffers)
   series_destroy(h);

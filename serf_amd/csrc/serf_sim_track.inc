@@ -131,9 +131,11 @@ __global__ __launch_bounds__(BLOCK) void track_count_kernel(Dev d, const uint4* 
             const u64 table = (u64)ta | ((u64)tc << 32);
             hit = up[k] && ((table >> (ek.w & 63u)) & 1u) && ek.z >= tb;
           } else {
-            hit = up[k] && (ek.w & SIM_VB_KNOWN) && E_LTIME(ek) >= ((u64)tb | ((u64)tc << 32));
+            hit = up[k] && view_applied(ek, (u64)tb | ((u64)tc << 32));
           }
         } else {
+          // bucket_holds (serf_sim_observe.inc) written out, without its test for key 0 (track_check refuses that key): this kernel
+          // uses every SGPR there is, and with the call — in any of the forms tried — the compiler spills two to six of them
           hit = up[k] && ((ek.z == ta) | (ek.w == ta));
           if (up[k] && !hit && ek.w) {  // the tail plane only when the head is full and does not hold the key
             const bool q = pkey >= TRK_PK_Q;
@@ -159,17 +161,8 @@ __global__ __launch_bounds__(BLOCK) void track_count_kernel(Dev d, const uint4* 
 __global__ __launch_bounds__(BLOCK) void track_resolve_kernel(TrkDevP p) {
   const u32 i = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= p.n) return;  // (whole waves)
-  u32 cs = 0, us = 0;
-  for (u32 g = lane; g < p.G; g += 64) {
-    cs += p.part[(size_t)i * p.G + g];
-    us += p.part[(size_t)p.n * p.G + g];
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    cs += __shfl_xor(cs, o);
-    us += __shfl_xor(us, o);
-  }
+  const u64 c = fold_row(p.part + (size_t)i * p.G, p.G, FOLD_SUM), up = fold_row(p.part + (size_t)p.n * p.G, p.G, FOLD_SUM);
   if (lane) return;
-  const u64 c = cs, up = us;
   const u32 id = p.items[i].id;
   sim_track_result r = p.res[id];
   if (r.state == 2) return;
@@ -316,11 +309,6 @@ static int track_fetch(sim_handle* h) {
   return SIM_OK;
 }
 
-static int track_usable(const sim_handle* h) {
-  if (!h) return SIM_EINVAL;
-  if (h->d.sharded || h->in_tick) return SIM_ESTATE;
-  return SIM_OK;
-}
 static int track_check(const sim_handle* h, const sim_tracker& t, TrkItem* it) {
   const Dev& d = h->d;
   memset(it, 0, sizeof *it);
@@ -354,7 +342,7 @@ extern "C" {
 uint32_t sim_track_version(void) { return SIM_TRACK_VERSION; }
 
 int sim_track_add(sim_handle* h, const sim_tracker* t, uint32_t n, uint32_t* ids_out) {
-  if (int rc = track_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!t || !ids_out || !n) return SIM_EINVAL;
   std::vector<TrkItem> items(std::min<u32>(n, SIM_TRACK_MAX + 1));
   for (u32 i = 0; i < n && i <= SIM_TRACK_MAX; ++i)
@@ -404,7 +392,7 @@ static int track_ids_ok(const sim_handle* h, const uint32_t* ids, uint32_t n, bo
 }
 
 int sim_track_remove(sim_handle* h, const uint32_t* ids, uint32_t n) {
-  if (int rc = track_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (n > SIM_TRACK_MAX) return SIM_EINVAL;
   if (int rc = track_ids_ok(h, ids, n, true)) return rc;
   TrackState* s = h->trk;
@@ -414,7 +402,7 @@ int sim_track_remove(sim_handle* h, const uint32_t* ids, uint32_t n) {
 }
 
 int sim_track_read(sim_handle* h, const uint32_t* ids, uint32_t n, sim_track_result* out) {
-  if (int rc = track_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!out) return SIM_EINVAL;
   if (int rc = track_ids_ok(h, ids, n, false)) return rc;
   if (int rc = track_fetch(h)) return rc;
@@ -423,7 +411,7 @@ int sim_track_read(sim_handle* h, const uint32_t* ids, uint32_t n, sim_track_res
 }
 
 int sim_track_active(sim_handle* h, uint32_t* registered, uint32_t* active) {
-  if (int rc = track_usable(h)) return rc;
+  if (int rc = observer_usable(h)) return rc;
   if (!registered || !active) return SIM_EINVAL;
   *registered = *active = 0;
   TrackState* s = h->trk;

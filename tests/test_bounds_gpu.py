@@ -91,6 +91,64 @@ def test_same_lamport_time_fills_a_bucket_and_its_overflow_rows(oracle, hiplib):
         o.close()
 
 
+def bucket_fill_states(ring, X, idx):
+    """Nodes by how far bucket idx of a dumped ring [X + B][n] has filled: [empty, head only (1-2 keys), tail in use (3-5),
+    full without overflow rows, with overflow rows] — the branches of the rumour predicate (serf_sim_observe.inc bucket_holds)."""
+    keys = (ring[X + idx]["keys"] != 0).sum(axis=1)
+    rows = (ring[:X]["ltime"] == idx + 1).sum(axis=0)
+    full = keys == _ffi.CKEYS
+    assert not (rows[~full] != 0).any(), "overflow rows behind a bucket that is not full"
+    return [int((keys == 0).sum()), int(((keys >= 1) & (keys <= 2)).sum()), int(((keys >= 3) & (keys < _ffi.CKEYS)).sum()),
+            int((full & (rows == 0)).sum()), int((rows != 0).sum())]
+
+
+def test_four_answers_agree_while_a_rumour_is_half_way(oracle, hiplib):
+    # the scenario of the test above, looked at while the 70 rumours travel: sim_convergence, sim_convergence_many, the trackers and the
+    # oracle answer "how many running nodes have applied it" alike, with buckets in every state the predicate distinguishes
+    n, X, Bev, Bq = 2048, 8, 32, 16
+    for rf in (False, True):
+        kw = dict(fanout=4, view_slots=64, event_ring=Bev, query_ring=Bq, ring_overflow=X, pkt_records=8)
+        if rf:
+            kw["flags"] = _ffi.CF_BASELINE_JOINED | _ffi.CF_RANDOM_FANOUT
+        g, o = pair(oracle, hiplib, n, **kw)
+        rows = o.dump(_ffi.ARR_ROWS)  # (nobody has originated anything: the Lamport times the operations of tick 2 will take)
+        lt_e, lt_q = int(rows["event_clock"].max()), int(rows["query_clock"].max())
+        assert lt_e == int(rows["event_clock"].min()) and lt_q == int(rows["query_clock"].min())
+        rumours = [(_ffi.K_EVENT, 1000 + i, lt_e) for i in range(40)] + [(_ffi.K_QUERY, 5000 + i, lt_q) for i in range(30)]
+        ids = g.track_add([_ffi.rumour_tracker(*r) for r in rumours])
+        ops = [(2, _ffi.OP_USER_EVENT, 17 * i + 3, 1000 + i, 40 + i) for i in range(40)] + \
+              [(2, _ffi.OP_QUERY, 29 * i + 5, 5000 + i, _ffi.F_ACK) for i in range(30)]
+        sc.apply_schedule(g, ops)
+        sc.apply_schedule(o, ops)
+        for tick, steps in ((6, 6), (8, 2)):
+            g.step(steps)
+            o.step(steps)
+            want = [o.convergence(*r) for r in rumours]
+            many = []
+            for b in range(0, len(rumours), 64):
+                seen, up = g.convergence_many(rumours[b:b + 64])
+                many += [(s, up) for s in seen]
+            res = g.track_read(ids)
+            for i, r in enumerate(rumours):
+                answers = {"convergence": g.convergence(*r), "convergence_many": many[i], "tracker": (res[i].last, res[i].last_up),
+                           "oracle": want[i]}
+                assert len(set(answers.values())) == 1, f"rf={rf} tick {tick} rumour {r}: {answers}"
+            # ... and the scenario is the one that was meant, by the oracle alone
+            er = o.dump(_ffi.ARR_ERING).reshape(X + Bev, n)
+            states = bucket_fill_states(er, X, lt_e % Bev)
+            print(f"rf={rf} tick {tick}: event bucket fill states {states}, counts {min(want)} .. {max(want)}")
+            assert all(up == n for _, up in want)
+            if tick == 6:
+                assert all(0 < seen < up for seen, up in want), "every rumour was meant to be half way"
+                assert min(states) >= 10, f"every fill state was meant to hold at least 10 nodes: {states}"
+            else:
+                assert 2 * states[4] > n, f"more than half the nodes were meant to use overflow rows: {states}"
+                assert all(seen < up for seen, up in want[:40]), "no event was meant to have arrived everywhere"
+        assert g.digest() == o.digest()
+        g.close()
+        o.close()
+
+
 def test_past_the_new_bounds_both_count_the_same_drops(oracle, hiplib):
     # a load no 64-slot queue and no 2 overflow rows hold: the bounds bite — identically
     n = 1024
