@@ -554,13 +554,16 @@ enum sim_array { SIM_ARR_ROWS = 0, SIM_ARR_QUEUE = 1, SIM_ARR_INBOX = 2, SIM_ARR
 int sim_dump_state(sim_handle* h, uint32_t which, void* buf, size_t cap_bytes, size_t* bytes);
 
 /* Rumor convergence: number of up nodes that have applied the message (kind,key,ltime) and
- * number of up nodes (rounds-to-99 % = first tick with seen >= 0.99 * up). */
+ * number of up nodes (rounds-to-99 % = first tick with seen >= 0.99 * up).
+ * EVENT / QUERY: key 0 is accepted and names no rumour (in a bucket it is an empty place): *seen = 0, *up the running nodes.
+ * JOIN / LEAVE: key is the subject, below n_nodes (SIM_EINVAL otherwise); a subject without a view slot sits at its baseline. */
 int sim_convergence(sim_handle* h, uint32_t kind, uint32_t key, uint64_t ltime,
                     uint64_t* seen, uint64_t* up);
 
 /* The same for n <= SIM_CONV_MAX rumours in ONE pass over the nodes (bench.py follows every user event of its workload
  * through a window of ticks: one launch per tick instead of one per rumour and tick): seen[i] for (kinds[i], keys[i],
- * ltimes[i]); `up` is the common denominator. */
+ * ltimes[i]); `up` is the common denominator.  Every entry is judged as sim_convergence judges it: key 0 of an EVENT / QUERY is
+ * accepted, seen[i] = 0 (sim_track_add, serf_sim_track.h, refuses that key: a tracker of nothing would never retire). */
 #define SIM_CONV_MAX 64u
 int sim_convergence_many(sim_handle* h, uint32_t n, const uint32_t* kinds, const uint32_t* keys, const uint64_t* ltimes,
                          uint64_t* seen, uint64_t* up);

@@ -1529,11 +1529,13 @@ int sim_convergence(sim_handle* h, uint32_t kind, uint32_t key, uint64_t ltime, 
   if (int lrc = conv_plane(h, kind, ltime)) return lrc;
   ConvSet cs;
   memset(&cs, 0, sizeof cs);
-  cs.n = 1; cs.kind[0] = kind; cs.key[0] = key; cs.ltime[0] = ltime;
-  u64 r[2];
+  // key 0 of an EVENT / QUERY is "an empty place" of a bucket, no rumour: nobody holds it, the pass only counts the running nodes
+  const bool nokey = !key && (kind == SIM_K_EVENT || kind == SIM_K_QUERY);
+  cs.n = nokey ? 0 : 1; cs.kind[0] = kind; cs.key[0] = key; cs.ltime[0] = ltime;
+  u64 r[2] = {0, 0};
   if (int rc = conv_run(h, cs, h->d_scratch + 8, r)) return rc;  // (the handle's own words: no allocation per call)
   *up = r[0];
-  *seen = r[1];
+  *seen = nokey ? 0 : r[1];
   return SIM_OK;
 }
 
@@ -1601,12 +1603,14 @@ int sim_convergence_many(sim_handle* h, uint32_t n, const uint32_t* kinds, const
   Dev& d = h->d;
   ConvSet cs;
   memset(&cs, 0, sizeof cs);
-  cs.n = n;
+  u32 at[SIM_CONV_MAX];  // the kernel's entry of rumour i; ~0: key 0 of an EVENT / QUERY, which nobody holds (sim_convergence)
   for (u32 i = 0; i < n; ++i) {
     if (kinds[i] == SIM_K_JOIN || kinds[i] == SIM_K_LEAVE) { if (keys[i] >= d.N) return SIM_EINVAL; }
     else if (kinds[i] != SIM_K_EVENT && kinds[i] != SIM_K_QUERY) return SIM_EINVAL;
-    else if (!keys[i]) return SIM_EINVAL;
-    cs.kind[i] = kinds[i]; cs.key[i] = keys[i]; cs.ltime[i] = ltimes[i];
+    else if (!keys[i]) { at[i] = ~0u; continue; }
+    at[i] = cs.n;
+    cs.kind[cs.n] = kinds[i]; cs.key[cs.n] = keys[i]; cs.ltime[cs.n] = ltimes[i];
+    cs.n++;
     if (int lrc = conv_plane(h, kinds[i], ltimes[i])) return lrc;
   }
   u64* scr = nullptr;
@@ -1616,7 +1620,7 @@ int sim_convergence_many(sim_handle* h, uint32_t n, const uint32_t* kinds, const
   (void)hipFree(scr);
   if (rc) return rc;
   *up = r[0];
-  for (u32 i = 0; i < n; ++i) seen[i] = r[1 + i];
+  for (u32 i = 0; i < n; ++i) seen[i] = at[i] == ~0u ? 0 : r[1 + at[i]];
   return SIM_OK;
 }
 
