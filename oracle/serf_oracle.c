@@ -2899,6 +2899,21 @@ int API(restore)(osim* s, const void* buf, size_t bytes) {
   snap_header h;
   memcpy(&h, buf, sizeof h);
   if (h.magic != SNAP_MAGIC || h.abi != SIM_ABI_VERSION || memcmp(&h.cfg, &s->cfg, sizeof(sim_config))) return SIM_EINVAL;
+  { /* every section length before anything is written: an image that is refused leaves the handle the fresh one it was */
+    const void* vptr[SNAP_SECTIONS];
+    size_t vlen[SNAP_SECTIONS];
+    snap_sections(s, vptr, vlen);
+    vlen[12] = (size_t)h.n_pending_ops * sizeof(sim_opent);
+    const uint8_t* in = (const uint8_t*)buf + sizeof h;
+    const uint8_t* end = (const uint8_t*)buf + bytes;
+    for (int i = 0; i < SNAP_SECTIONS; ++i) {
+      uint64_t n;
+      if ((size_t)(end - in) < 8) return SIM_EINVAL;
+      memcpy(&n, in, 8); in += 8;
+      if (n != vlen[i] || (size_t)(end - in) < n) return SIM_EINVAL;
+      in += n;
+    }
+  }
   s->tick = h.tick;
   s->n_slots = h.n_slots;
   s->ops_dropped = h.ops_dropped; s->slots_recycled = h.slots_recycled;

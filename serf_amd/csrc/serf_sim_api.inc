@@ -16,68 +16,15 @@ const char* sim_backend_name(void) { return "hip-gfx950"; }
 
 int sim_destroy(sim_handle* h) {
   if (!h) return SIM_EINVAL;
-  (void)hipStreamSynchronize(h->stream);
-  if (h->xstream) (void)hipStreamSynchronize(h->xstream);
-  if (h->trk) track_destroy(h);
-  if (h->ser) series_destroy(h);
-  if (h->cen) census_destroy(h);
-  if (h->xcomm) (void)ncclCommDestroy(h->xcomm);
-  if (h->xstream) (void)hipStreamDestroy(h->xstream);
-  if (h->xev_go) (void)hipEventDestroy(h->xev_go);
-  if (h->xev_done) (void)hipEventDestroy(h->xev_done);
-  for (int i = 0; i < 4; ++i) if (h->xh_ev[i]) (void)hipEventDestroy(h->xh_ev[i]);
-  if (h->xh_dev) (void)hipFree(h->xh_dev);
-  if (h->xh_host) (void)hipHostFree(h->xh_host);
-  if (h->rf_stream) { (void)hipStreamSynchronize(h->rf_stream); (void)hipStreamDestroy(h->rf_stream); }
-  for (int i = 0; i < 3; ++i) if (h->rf_done[i]) (void)hipEventDestroy(h->rf_done[i]);
-  for (int i = 0; i < 2; ++i) if (h->rf_go[i]) (void)hipEventDestroy(h->rf_go[i]);
-  for (auto& pr : h->prof) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  if (h->d_pp) (void)hipFree(h->d_pp);
-  for (int i = 0; i < 3; ++i) {
-    if (h->sreq_host[i]) (void)hipHostFree(h->sreq_host[i]);
-    if (h->sreq_ev[i]) (void)hipEventDestroy(h->sreq_ev[i]);
-  }
-  if (h->xflag) (void)hipHostFree(h->xflag);
-  if (h->deep_seen) (void)hipHostFree(h->deep_seen);
-  for (void* p : h->allocs) (void)hipFree(p);
-  lazy_release(h->lz_view); lazy_release(h->lz_ev); lazy_release(h->lz_q);
-  delete h;
+  delete h;  // (~sim_handle, serf_sim_host.inc)
   return SIM_OK;
 }
 
-int sim_create(const sim_config* cfg, sim_handle** out) {
-  int rc = cfg_check(cfg);
-  if (rc) return rc;
-  if (!out) return SIM_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    fprintf(stderr, "serf_sim: no HIP device available (this library has no CPU fallback)\n");
-    return SIM_EDEVICE;
-  }
-  sim_handle* h = new sim_handle();
-  h->cfg = *cfg;
-  h->tick = 0;
-  h->stream = nullptr;
-  h->op_cursor = 0;
-  h->bound = false;
-  h->n_alloc = 0; h->ops_dropped = h->slots_recycled = 0; h->recycle_at = 0xFFFFFFFFu;
-  h->pp_done_at = 0xFFFFFFFFu; h->d_pp = nullptr;
-  h->rc_refd = nullptr; h->rc_scr = nullptr;
-  for (int i = 0; i < 3; ++i) { h->sreq_host[i] = nullptr; h->sreq_ev[i] = nullptr; h->sreq_buf[i] = nullptr; h->sreq_wait[i] = nullptr; }
-  h->sreq_on_dispatch = false;
-  h->deep_seen = nullptr;
-  h->in_tick = false;
-  h->tick_timed = false;
-  h->rbuf[0] = h->rbuf[1] = nullptr;
-  h->xcomm = nullptr; h->xstream = nullptr; h->xev_go = h->xev_done = nullptr; h->xworld = 0; h->xpending = false; h->self_direct = false;
-  h->xh_dev = h->xh_host = nullptr;
-  for (int i = 0; i < 4; ++i) { h->xh_ev[i] = nullptr; h->xh_tick[i] = ~0ull; }
-  h->profiling = 0;
-  h->prof_seq = 0;
-  memset(&h->prev, 0, sizeof h->prev);
-  (void)hipGetDevice(&h->device);
+// ---- sim_create, step by step (a step that fails returns its code: the handle's destructor gives back what the steps before it got) ----
+// the Dev scalars and the handle's own parameters, from the configuration
+static void create_params(sim_handle* h) {
+  const sim_config* cfg = &h->cfg;
   Dev& d = h->d;
-  memset(&d, 0, sizeof d);
   d.N = cfg->n_nodes; d.V = cfg->vshards; d.M = d.N / d.V;
   d.sharded = cfg->shard_count > 1 || (cfg->flags & SIM_CF_FORCE_SHARDED);  // (the flag: ONE shard run as a shard — the N > 1 path with a single rank)
   d.Nl = d.sharded ? d.M : d.N;
@@ -91,7 +38,6 @@ int sim_create(const sim_config* cfg, sim_handle** out) {
   d.PG = d.P / SIM_P;
   d.fp = d.f * d.PG;
   d.npend = d.f * d.P + SIM_S + 1u + ((cfg->flags & SIM_CF_RANDOM_FANOUT) ? SIM_RF_PEND_EXTRA : 0u);
-  d.vtail = (size_t)d.A * d.Nl; d.etail = (size_t)(d.X + d.Bev) * d.Nl; d.qtail = (size_t)(d.X + d.Bq) * d.Nl;
   d.bev_mask = (d.Bev > 1 && !(d.Bev & (d.Bev - 1))) ? d.Bev - 1 : 0;
   d.bq_mask = (d.Bq > 1 && !(d.Bq & (d.Bq - 1))) ? d.Bq - 1 : 0;
   d.retransmit_mult = cfg->retransmit_mult;
@@ -111,9 +57,7 @@ int sim_create(const sim_config* cfg, sim_handle** out) {
   d.gttd = cfg->gossip_to_the_dead;
   d.rfan = (cfg->flags & SIM_CF_RANDOM_FANOUT) ? 1u : 0u;
   d.prune_delay = (cfg->flags & SIM_CF_PRUNE_DELAY) ? 1u : 0u;
-  h->qt_cursor = 0;
   h->q_timeout = 16u * h_digits10(cfg->n_nodes);  // query.rs:421-427, query_timeout_mult = 16 (options.rs:518)
-  h->pp_step = 0;
   if (cfg->push_pull_interval) {  // memberlist pushPullScale: x (ceil(log2 N - 5) + 1) above 32 nodes
     u64 mult = 1;
     if (cfg->n_nodes > 32) mult = (u64)std::ceil(std::log2((double)cfg->n_nodes) - 5.0) + 1;
@@ -121,18 +65,16 @@ int sim_create(const sim_config* cfg, sim_handle** out) {
     h->pp_step = st < 1 ? 1u : st > 0x7FFFFFFFu ? 0x7FFFFFFFu : (u32)st;
   }
   d.ev_cap = EV_CAP;
-  size_t Nl = d.Nl, nup = ((size_t)d.N + 31) / 32;
-#define DA(ptr, n)                                   \
-  if ((rc = dalloc(h, &(ptr), (n))) != SIM_OK) {     \
-    sim_destroy(h);                                  \
-    return rc;                                       \
-  }
+}
+#define DA(ptr, n) \
+  if (int rc_ = dalloc(h, &(ptr), (n))) return rc_;
+// the device memory that lives as long as the handle
+static int create_alloc(sim_handle* h) {
+  Dev& d = h->d;
+  const size_t Nl = d.Nl, nup = ((size_t)d.N + 31) / 32;
   DA(d.R0, Nl) DA(d.R1, Nl) DA(d.R2, Nl) DA(d.R3, Nl) DA(d.R4, 2 * Nl) DA(d.R5, Nl)
   DA(d.qkeys, (size_t)(SIM_Q / 4u) * Nl) DA(d.qpay, (size_t)SIM_Q * Nl) DA(d.pend, (size_t)d.npend * Nl)
   DA(d.qused, Nl) DA(d.deep_list, 2 * Nl) DA(d.deep_cnt, 4)
-  d.deep_par = 0;
-  h->inbox_mat = nullptr;
-  h->mat_tick = ~0ull;
   if (!d.sharded) {
     const size_t cu4 = d.rfan ? RF_CELL_U4 : PK_U4;  // (random fan-out: 64-byte cells, the map word inside cell 0)
     DA(d.obox[0], (size_t)d.fp * Nl * cu4) DA(d.obox[1], (size_t)d.fp * Nl * cu4)
@@ -146,12 +88,20 @@ int sim_create(const sim_config* cfg, sim_handle** out) {
   }
   // view entries and ring buckets: planes that get their memory when a slot / a Lamport time first needs them (LazyPlanes,
   // serf_sim_host.inc) where the planes are mappable units; whole otherwise
-  h->ev_hi = h->q_hi = 1;
-  if (h->dense || !lazy_reserve(h, h->lz_view, &d.view, d.A, Nl)) DA(d.view, (size_t)d.A * Nl * 2)
   // (the rings of a shard are whole: ev_hi / q_hi bound the cluster's clocks only when every shard hears of every record that
   // comes in over the byte boundary — slots, by contrast, are handed out by replicated bookkeeping)
-  if (d.sharded || !lazy_reserve(h, h->lz_ev, &d.ering0, d.X + d.Bev, Nl)) DA(d.ering0, (size_t)(d.X + d.Bev) * Nl * 2)
-  if (d.sharded || !lazy_reserve(h, h->lz_q, &d.qring0, d.X + d.Bq, Nl)) DA(d.qring0, (size_t)(d.X + d.Bq) * Nl * 2)
+  const u32 planes[SP_N] = {d.A, d.X + d.Bev, d.X + d.Bq};
+  for (int i = 0; i < SP_N; ++i) {
+    SplitArr& A = h->sp[i];
+    A.planes = planes[i];
+    A.tail = (size_t)planes[i] * Nl;
+    const bool whole = i == SP_VIEW ? h->dense : d.sharded;
+    if (whole || !lazy_reserve(h, A.lz, &A.base, A.planes, Nl)) DA(A.base, A.tail * 2)
+  }
+  // the kernels' copy
+  d.view = h->sp[SP_VIEW].base; d.vtail = h->sp[SP_VIEW].tail;
+  d.ering0 = h->sp[SP_EV].base; d.etail = h->sp[SP_EV].tail;
+  d.qring0 = h->sp[SP_Q].base; d.qtail = h->sp[SP_Q].tail;
   d.ering = d.ering0 + (size_t)d.X * Nl; d.qring = d.qring0 + (size_t)d.X * Nl;  // bucket i = row X + i: the overflow rows come first (they are always mapped)
   DA(d.slot_of, d.N) DA(d.subject_of, d.A) DA(d.walk, d.A) DA(d.upmap, nup) DA(d.nullcell, 4) DA(d.skipmask, (d.gttd || d.rfan) ? Nl : 1) DA(h->sreq_buf[0], 1 + 2 * SIM_SUSPECT_REQ_MAX) DA(h->sreq_buf[1], 1 + 2 * SIM_SUSPECT_REQ_MAX) DA(h->sreq_buf[2], 1 + 2 * SIM_SUSPECT_REQ_MAX)
   DA(d.qtab, QTAB_U4(d.N)) DA(d.qbits, (size_t)SIM_QT * 2 * nup)
@@ -161,108 +111,111 @@ int sim_create(const sim_config* cfg, sim_handle** out) {
   DA(h->d_mst, d.N)
   DA(h->d_mlt, d.N)
   DA(h->d_stats, 1)
-  d.rcsr = d.rsrc = nullptr;
-  for (int i = 0; i < 3; ++i) { h->rf_rcsr[i] = h->rf_rsrc[i] = nullptr; h->rf_cntb[i] = nullptr; h->rf_btot[i] = h->rf_xoff[i] = nullptr; }
-  h->rx_rcsr = h->rx_rsrc = nullptr; h->xflag = nullptr; h->rf_C = 1u;
-  memset(&h->rfx, 0, sizeof h->rfx);
-  h->rf_stream = nullptr; h->rf_go[0] = h->rf_go[1] = nullptr;
-  for (int i = 0; i < 3; ++i) { h->rf_done[i] = nullptr; h->rf_q[i] = ~0ull; }
-  h->rf_gcur[0] = h->rf_gcur[1] = nullptr; h->rf_ovf[0] = h->rf_ovf[1] = h->rf_l1 = nullptr; h->rf_par = 0; h->rf_wide = false;
-  memset(&h->rfp, 0, sizeof h->rfp);
-  if (d.rfan) {  // the fan-out graph as a CSR, rebuilt every tick (SIM_CF_RANDOM_FANOUT)
-    RfP& r = h->rfp;
-    r.N = d.N; r.Nl = d.Nl; r.shard0 = d.shard0; r.f = d.f;
-    r.Ns = d.Nl;  // every handle sorts the pairs of its OWN senders: by (local) target — or, a shard, by target anywhere in the cluster
-    r.V = d.sharded ? d.V : 1u; r.M = d.sharded ? d.M : d.N;
-    if (d.sharded && d.V > 64u) { sim_destroy(h); return SIM_EINVAL; }
-    // the sorted list: every pair of the handle's senders, f * Nl at most.  The rows a shard RECEIVES (rx_rsrc): f * Nl on average
-    const size_t np = (size_t)d.f * Nl, nrx = (size_t)d.f * Nl + (size_t)(12.0 * std::sqrt((double)d.f * Nl)) + 4096u;
-    r.rcap = (u32)np;
-    // level-1 buckets of 2^LB targets.  A scattered entry carries the pair id (PB bits) and the target's offset in its bucket
-    // (LB bits) — rf_rows does not draw again —; 32-bit entries when both fit (1 Mi nodes: 22 + 10), 64-bit ones otherwise.
-    // A shard's buckets are per destination (V * ceil(M / 2^LB) of them): narrow entries while that keeps rf_scatter's three
-    // tables in 48 KiB of LDS, else wide ones and about 2048 buckets
-    r.PB = 1;
-    while ((1ull << r.PB) < 4ull * r.Ns) r.PB++;
-    auto nb_of = [&](u32 lb) { return (size_t)r.V * (((size_t)r.M + (1u << lb) - 1u) >> lb); };
-    r.LB = std::min<u32>(11u, 32u - std::min<u32>(r.PB, 24u));
-    if (const char* e = getenv("SERF_RF_LB")) r.LB = std::min<u32>(RF_LB_MAX, std::max<u32>(8u, (u32)strtoul(e, nullptr, 0)));
-    while (nb_of(r.LB) > (r.V > 1u && r.PB + r.LB > 32u ? 2048u : 4096u) && r.LB < RF_LB_MAX) r.LB++;  // rf_scatter's three tables: 48 KiB of LDS next to its staging area
-    if (nb_of(r.LB) > 4096u) { sim_destroy(h); return SIM_EINVAL; }
-    h->rf_wide = r.PB + r.LB > 32u || getenv("SERF_RF_WIDE") != nullptr;
-    r.NBh = (u32)(nb_of(r.LB) / r.V);
-    r.NB = r.V * r.NBh;
-    r.NWG = (u32)(((size_t)r.Ns + (h->rf_wide ? RfSpw<u64>::v : RfSpw<u32>::v) - 1u) / (h->rf_wide ? RfSpw<u64>::v : RfSpw<u32>::v));
-    // pairs of a bucket: f per row on one handle; a shard's f * M pairs spread over all V * NBh buckets
-    const double mean = (double)d.f * (double)(1u << r.LB) / (double)r.V;
-    r.cap = std::min<u32>(std::max<u32>(((u32)(mean + 16.0 * std::sqrt(mean)) + 64u + RFR - 1u) / RFR * RFR, RFR), RF_EPT * RFR);  // 16 sigma and more of room
-    if (r.V == 1u) r.cap = std::min<u32>(6u << r.LB, std::max<u32>(r.cap, RFR));  // one handle: mean f * 2^LB and 16 sigma, rounded up to the workgroup (5 632 at 1 Mi nodes: 11 pairs per thread)
-    if (const char* e = getenv("SERF_RF_CAP")) r.cap = std::max<u32>(RFR, std::min<u32>(r.cap, (u32)strtoul(e, nullptr, 0)) / RFR * RFR);  // tests: force rf_rows' slow path
-    // a bucket's region of l1: the mean and 12 sigma; what does not fit goes onto the overflow list
-    {
-      r.bcap = (u32)(mean + 12.0 * std::sqrt(mean)) + 64u;
-      if (const char* e = getenv("SERF_RF_BCAP")) r.bcap = std::max<u32>(1u, (u32)strtoul(e, nullptr, 0));  // tests: force the overflow list
-      r.ocap = (u32)np;  // (every pair would fit: the list cannot run full)
-    }
-    {
-      const int rl = (int)rf_rows_lds(r);
-      bool bad;
-      if (h->rf_wide) bad = hipFuncSetAttribute(reinterpret_cast<const void*>(rf_rows_kernel<u64, RF_EPT, (1u << RF_LB_MAX) / RFR>), hipFuncAttributeMaxDynamicSharedMemorySize, rl) != hipSuccess ||
-                            hipFuncSetAttribute(reinterpret_cast<const void*>(rf_rows_kernel<u64, 11u, 2u>), hipFuncAttributeMaxDynamicSharedMemorySize, rl) != hipSuccess ||
-                            hipFuncSetAttribute(reinterpret_cast<const void*>(rf_scatter_kernel<u64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rf_scatter_lds<u64>(r)) != hipSuccess;
-      else bad = hipFuncSetAttribute(reinterpret_cast<const void*>(rf_rows_kernel<u32, RF_EPT, (1u << RF_LB_MAX) / RFR>), hipFuncAttributeMaxDynamicSharedMemorySize, rl) != hipSuccess ||
-                 hipFuncSetAttribute(reinterpret_cast<const void*>(rf_rows_kernel<u32, 11u, 2u>), hipFuncAttributeMaxDynamicSharedMemorySize, rl) != hipSuccess ||
-                 hipFuncSetAttribute(reinterpret_cast<const void*>(rf_scatter_kernel<u32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rf_scatter_lds<u32>(r)) != hipSuccess;
-      if (bad) { sim_destroy(h); return SIM_EDEVICE; }
-    }
-    if (hipHostMalloc((void**)&h->xflag, 64) != hipSuccess) { sim_destroy(h); return SIM_ENOMEM; }
-    *h->xflag = 0;
-    if (d.sharded) {
-      h->rf_C = cfg->chunks > 1 ? cfg->chunks : 1u;  // sender chunks: each packed and exchanged behind its own launch
-      h->rfx = rfx_layout(d.V, h->rf_C, d.M, r.NBh, r.LB, d.PG, d.f);
-      if ((size_t)h->rf_C * d.V * h->rfx.slab_u >= ((size_t)1 << 30) ||   // rfx_index_kernel's 32-bit cell index: the receive buffer holds C * V slabs (ADVICE r5)
-          hipFuncSetAttribute(reinterpret_cast<const void*>(rfx_index_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rfx_index_lds(h->rfx)) != hipSuccess) { sim_destroy(h); return SIM_EINVAL; }
-      for (int i = 0; i < 3; ++i) { DA(h->rf_cntb[i], (size_t)d.N * h->rf_C) DA(h->rf_btot[i], (size_t)r.NB * h->rf_C) DA(h->rf_xoff[i], (2 * (size_t)d.V + 2) * h->rf_C) }
-      DA(h->rx_rcsr, Nl + 1) DA(h->rx_rsrc, nrx)
-      if (hipMemset(h->rx_rcsr, 0, (Nl + 1) * 4) != hipSuccess) { sim_destroy(h); return SIM_EDEVICE; }  // tick 0 receives nothing
-    }
-    h->rf_sync = getenv("SERF_RF_SYNC") != nullptr;  // measurements: build on the tick's own stream, nothing overlaps
-    {  // no packets of our own between two tick kernels (sim_step_begin): on unless SERF_RF_LEAN=0
-      const char* e = getenv("SERF_RF_LEAN");
-      h->rf_lean = !(e && *e == '0');
-    }
-    for (int i = 0; i < 3; ++i) { DA(h->rf_rcsr[i], Nl + 1) DA(h->rf_rsrc[i], np) }
-    h->rx_cap = (u32)nrx;
-    {
-      const size_t esz = h->rf_wide ? 2 : 1;  // (in u32 words)
-      u32* p32 = nullptr;
-      for (int i = 0; i < 2; ++i) { DA(h->rf_gcur[i], (size_t)r.NB * RF_GCS) DA(p32, (1 + 2 * (size_t)r.ocap) * esz) h->rf_ovf[i] = p32; }
-      DA(p32, (size_t)r.NB * r.bcap * esz)
-      h->rf_l1 = p32;
-    }
-    bool ok = true;
-    for (int i = 0; i < 3; ++i) ok = ok && hipMemset(h->rf_rcsr[i], 0, (Nl + 1) * 4) == hipSuccess;  // tick 0 receives nothing
-    for (int i = 0; i < 2; ++i) ok = ok && hipMemset(h->rf_gcur[i], 0, (size_t)r.NB * RF_GCS * 4) == hipSuccess && hipMemset(h->rf_ovf[i], 0, 8) == hipSuccess;
-    {  // the build stream; SERF_RF_PRIO=high|low: at the highest / lowest stream priority (measurements)
-      int plo = 0, phi = 0;
-      const char* pe = getenv("SERF_RF_PRIO");
-      // (r6) a shard: at the highest priority — a priority level has hardware queues of its own, and a process that also holds an
-      // exchange stream, torch's streams and RCCL's found the build sharing the handle's queue: every build ran between two tick
-      // kernels instead of beside one (profiles/r06_experiments.md §7)
-      if (!pe && d.sharded) pe = "high";
-      if (pe && *pe != 'n' && hipDeviceGetStreamPriorityRange(&plo, &phi) == hipSuccess)
-        ok = ok && hipStreamCreateWithPriority(&h->rf_stream, hipStreamNonBlocking, *pe == 'h' ? phi : plo) == hipSuccess;
-      else ok = ok && hipStreamCreateWithFlags(&h->rf_stream, hipStreamNonBlocking) == hipSuccess;
-    }
-    ok = ok &&
-         hipEventCreateWithFlags(&h->rf_done[0], hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&h->rf_done[1], hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&h->rf_done[2], hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&h->rf_go[0], hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&h->rf_go[1], hipEventDisableTiming) == hipSuccess;
-    if (!ok) { sim_destroy(h); return SIM_EDEVICE; }
+  return SIM_OK;
+}
+// the fan-out graph as a CSR, rebuilt every tick (SIM_CF_RANDOM_FANOUT): its parameters, scratch, stream and events
+static int create_rf(sim_handle* h) {
+  const sim_config* cfg = &h->cfg;
+  Dev& d = h->d;
+  const size_t Nl = d.Nl;
+  RfP& r = h->rfp;
+  r.N = d.N; r.Nl = d.Nl; r.shard0 = d.shard0; r.f = d.f;
+  r.Ns = d.Nl;  // every handle sorts the pairs of its OWN senders: by (local) target — or, a shard, by target anywhere in the cluster
+  r.V = d.sharded ? d.V : 1u; r.M = d.sharded ? d.M : d.N;
+  if (d.sharded && d.V > 64u) return SIM_EINVAL;
+  // the sorted list: every pair of the handle's senders, f * Nl at most.  The rows a shard RECEIVES (rx_rsrc): f * Nl on average
+  const size_t np = (size_t)d.f * Nl, nrx = (size_t)d.f * Nl + (size_t)(12.0 * std::sqrt((double)d.f * Nl)) + 4096u;
+  r.rcap = (u32)np;
+  // level-1 buckets of 2^LB targets.  A scattered entry carries the pair id (PB bits) and the target's offset in its bucket
+  // (LB bits) — rf_rows does not draw again —; 32-bit entries when both fit (1 Mi nodes: 22 + 10), 64-bit ones otherwise.
+  // A shard's buckets are per destination (V * ceil(M / 2^LB) of them): narrow entries while that keeps rf_scatter's three
+  // tables in 48 KiB of LDS, else wide ones and about 2048 buckets
+  r.PB = 1;
+  while ((1ull << r.PB) < 4ull * r.Ns) r.PB++;
+  auto nb_of = [&](u32 lb) { return (size_t)r.V * (((size_t)r.M + (1u << lb) - 1u) >> lb); };
+  r.LB = std::min<u32>(11u, 32u - std::min<u32>(r.PB, 24u));
+  if (const char* e = getenv("SERF_RF_LB")) r.LB = std::min<u32>(RF_LB_MAX, std::max<u32>(8u, (u32)strtoul(e, nullptr, 0)));
+  while (nb_of(r.LB) > (r.V > 1u && r.PB + r.LB > 32u ? 2048u : 4096u) && r.LB < RF_LB_MAX) r.LB++;  // rf_scatter's three tables: 48 KiB of LDS next to its staging area
+  if (nb_of(r.LB) > 4096u) return SIM_EINVAL;
+  h->rf_wide = r.PB + r.LB > 32u || getenv("SERF_RF_WIDE") != nullptr;
+  r.NBh = (u32)(nb_of(r.LB) / r.V);
+  r.NB = r.V * r.NBh;
+  r.NWG = (u32)(((size_t)r.Ns + (h->rf_wide ? RfSpw<u64>::v : RfSpw<u32>::v) - 1u) / (h->rf_wide ? RfSpw<u64>::v : RfSpw<u32>::v));
+  // pairs of a bucket: f per row on one handle; a shard's f * M pairs spread over all V * NBh buckets
+  const double mean = (double)d.f * (double)(1u << r.LB) / (double)r.V;
+  r.cap = std::min<u32>(std::max<u32>(((u32)(mean + 16.0 * std::sqrt(mean)) + 64u + RFR - 1u) / RFR * RFR, RFR), RF_EPT * RFR);  // 16 sigma and more of room
+  if (r.V == 1u) r.cap = std::min<u32>(6u << r.LB, std::max<u32>(r.cap, RFR));  // one handle: mean f * 2^LB and 16 sigma, rounded up to the workgroup (5 632 at 1 Mi nodes: 11 pairs per thread)
+  if (const char* e = getenv("SERF_RF_CAP")) r.cap = std::max<u32>(RFR, std::min<u32>(r.cap, (u32)strtoul(e, nullptr, 0)) / RFR * RFR);  // tests: force rf_rows' slow path
+  // a bucket's region of l1: the mean and 12 sigma; what does not fit goes onto the overflow list
+  {
+    r.bcap = (u32)(mean + 12.0 * std::sqrt(mean)) + 64u;
+    if (const char* e = getenv("SERF_RF_BCAP")) r.bcap = std::max<u32>(1u, (u32)strtoul(e, nullptr, 0));  // tests: force the overflow list
+    r.ocap = (u32)np;  // (every pair would fit: the list cannot run full)
   }
+  {
+    const int rl = (int)rf_rows_lds(r);
+    bool bad;
+    if (h->rf_wide) bad = hipFuncSetAttribute(reinterpret_cast<const void*>(rf_rows_kernel<u64, RF_EPT, (1u << RF_LB_MAX) / RFR>), hipFuncAttributeMaxDynamicSharedMemorySize, rl) != hipSuccess ||
+                          hipFuncSetAttribute(reinterpret_cast<const void*>(rf_rows_kernel<u64, 11u, 2u>), hipFuncAttributeMaxDynamicSharedMemorySize, rl) != hipSuccess ||
+                          hipFuncSetAttribute(reinterpret_cast<const void*>(rf_scatter_kernel<u64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rf_scatter_lds<u64>(r)) != hipSuccess;
+    else bad = hipFuncSetAttribute(reinterpret_cast<const void*>(rf_rows_kernel<u32, RF_EPT, (1u << RF_LB_MAX) / RFR>), hipFuncAttributeMaxDynamicSharedMemorySize, rl) != hipSuccess ||
+               hipFuncSetAttribute(reinterpret_cast<const void*>(rf_rows_kernel<u32, 11u, 2u>), hipFuncAttributeMaxDynamicSharedMemorySize, rl) != hipSuccess ||
+               hipFuncSetAttribute(reinterpret_cast<const void*>(rf_scatter_kernel<u32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rf_scatter_lds<u32>(r)) != hipSuccess;
+    if (bad) return SIM_EDEVICE;
+  }
+  if (hipHostMalloc((void**)&h->xflag, 64) != hipSuccess) return SIM_ENOMEM;
+  *h->xflag = 0;
+  if (d.sharded) {
+    h->rf_C = cfg->chunks > 1 ? cfg->chunks : 1u;  // sender chunks: each packed and exchanged behind its own launch
+    h->rfx = rfx_layout(d.V, h->rf_C, d.M, r.NBh, r.LB, d.PG, d.f);
+    if ((size_t)h->rf_C * d.V * h->rfx.slab_u >= ((size_t)1 << 30) ||   // rfx_index_kernel's 32-bit cell index: the receive buffer holds C * V slabs (ADVICE r5)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(rfx_index_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rfx_index_lds(h->rfx)) != hipSuccess) return SIM_EINVAL;
+    for (int i = 0; i < 3; ++i) { DA(h->rf_cntb[i], (size_t)d.N * h->rf_C) DA(h->rf_btot[i], (size_t)r.NB * h->rf_C) DA(h->rf_xoff[i], (2 * (size_t)d.V + 2) * h->rf_C) }
+    DA(h->rx_rcsr, Nl + 1) DA(h->rx_rsrc, nrx)
+    if (hipMemset(h->rx_rcsr, 0, (Nl + 1) * 4) != hipSuccess) return SIM_EDEVICE;  // tick 0 receives nothing
+  }
+  h->rf_sync = getenv("SERF_RF_SYNC") != nullptr;  // measurements: build on the tick's own stream, nothing overlaps
+  {  // no packets of our own between two tick kernels (sim_step_begin): on unless SERF_RF_LEAN=0
+    const char* e = getenv("SERF_RF_LEAN");
+    h->rf_lean = !(e && *e == '0');
+  }
+  for (int i = 0; i < 3; ++i) { DA(h->rf_rcsr[i], Nl + 1) DA(h->rf_rsrc[i], np) }
+  h->rx_cap = (u32)nrx;
+  {
+    const size_t esz = h->rf_wide ? 2 : 1;  // (in u32 words)
+    u32* p32 = nullptr;
+    for (int i = 0; i < 2; ++i) { DA(h->rf_gcur[i], (size_t)r.NB * RF_GCS) DA(p32, (1 + 2 * (size_t)r.ocap) * esz) h->rf_ovf[i] = p32; }
+    DA(p32, (size_t)r.NB * r.bcap * esz)
+    h->rf_l1 = p32;
+  }
+  bool ok = true;
+  for (int i = 0; i < 3; ++i) ok = ok && hipMemset(h->rf_rcsr[i], 0, (Nl + 1) * 4) == hipSuccess;  // tick 0 receives nothing
+  for (int i = 0; i < 2; ++i) ok = ok && hipMemset(h->rf_gcur[i], 0, (size_t)r.NB * RF_GCS * 4) == hipSuccess && hipMemset(h->rf_ovf[i], 0, 8) == hipSuccess;
+  {  // the build stream; SERF_RF_PRIO=high|low: at the highest / lowest stream priority (measurements)
+    int plo = 0, phi = 0;
+    const char* pe = getenv("SERF_RF_PRIO");
+    // (r6) a shard: at the highest priority — a priority level has hardware queues of its own, and a process that also holds an
+    // exchange stream, torch's streams and RCCL's found the build sharing the handle's queue: every build ran between two tick
+    // kernels instead of beside one (profiles/r06_experiments.md §7)
+    if (!pe && d.sharded) pe = "high";
+    if (pe && *pe != 'n' && hipDeviceGetStreamPriorityRange(&plo, &phi) == hipSuccess)
+      ok = ok && hipStreamCreateWithPriority(&h->rf_stream, hipStreamNonBlocking, *pe == 'h' ? phi : plo) == hipSuccess;
+    else ok = ok && hipStreamCreateWithFlags(&h->rf_stream, hipStreamNonBlocking) == hipSuccess;
+  }
+  ok = ok &&
+       hipEventCreateWithFlags(&h->rf_done[0], hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&h->rf_done[1], hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&h->rf_done[2], hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&h->rf_go[0], hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&h->rf_go[1], hipEventDisableTiming) == hipSuccess;
+  return ok ? SIM_OK : SIM_EDEVICE;
+}
 #undef DA
+// the state of tick 0, on the handle's stream
+static int create_state(sim_handle* h) {
+  const sim_config* cfg = &h->cfg;
+  Dev& d = h->d;
+  const size_t Nl = d.Nl, nup = ((size_t)d.N + 31) / 32;
   bool joined = cfg->flags & SIM_CF_BASELINE_JOINED;
   hipStream_t s = h->stream;
   auto zero = [&](void* p, size_t bytes) { return hipMemsetAsync(p, 0, bytes, s); };
@@ -276,7 +229,6 @@ int sim_create(const sim_config* cfg, sim_handle** out) {
     HCHECK(hipHostMalloc((void**)&h->sreq_host[i], 2 * SREQ_HEAD * 4));
     memset(h->sreq_host[i], 0xFF, 2 * SREQ_HEAD * 4);
     HCHECK(hipEventCreateWithFlags(&h->sreq_ev[i], hipEventDisableTiming));
-    h->sreq_tick[i] = ~0ull;
   }
   HCHECK(zero(d.qtab, QTAB_U4(d.N) * 16)); HCHECK(zero(d.qbits, (size_t)SIM_QT * 2 * nup * 4));
   if (!d.sharded && !d.rfan) {  // nothing has been sent yet
@@ -287,10 +239,9 @@ int sim_create(const sim_config* cfg, sim_handle** out) {
     HCHECK(hipMemsetAsync(d.obox[0], 0xFF, (size_t)d.fp * Nl * RF_CELL_U4 * 16, s));
     if (d.obox[1] != d.obox[0]) HCHECK(hipMemsetAsync(d.obox[1], 0xFF, (size_t)d.fp * Nl * RF_CELL_U4 * 16, s));
   }
-  if (!h->lz_view.va) HCHECK(zero(d.view, (size_t)d.A * Nl * 32));
-  if (!h->lz_ev.va) HCHECK(zero(d.ering0, (size_t)(d.X + d.Bev) * Nl * 32));
-  if (!h->lz_q.va) HCHECK(zero(d.qring0, (size_t)(d.X + d.Bq) * Nl * 32));
-  if ((rc = rings_need(h)) != SIM_OK) { sim_destroy(h); return rc; }
+  for (SplitArr& A : h->sp)
+    if (!A.lz.va) HCHECK(zero(A.base, A.tail * 32));
+  if (int rc = rings_need(h)) return rc;
   HCHECK(hipMemsetAsync(d.upmap, 0xFF, nup * 4, s));
   // base.rs:196-205: every clock starts at 1 (+ the own join at ltime 1 when pre-joined)
   fill_u4<<<grid_for(Nl), BLOCK, 0, s>>>(d.R0, Nl, make_uint4(joined ? 2 : 1, 0, 1, 0));
@@ -328,7 +279,25 @@ int sim_create(const sim_config* cfg, sim_handle** out) {
   HCHECK(hipMemcpyAsync(d.subject_of, h->subject_of.data(), (size_t)d.A * 4, hipMemcpyHostToDevice, s));
   HCHECK(hipStreamSynchronize(s));
   HCHECK(hipGetLastError());
-  *out = h;
+  return SIM_OK;
+}
+int sim_create(const sim_config* cfg, sim_handle** out) {
+  int rc = cfg_check(cfg);
+  if (rc) return rc;
+  if (!out) return SIM_EINVAL;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    fprintf(stderr, "serf_sim: no HIP device available (this library has no CPU fallback)\n");
+    return SIM_EDEVICE;
+  }
+  std::unique_ptr<sim_handle> h(new sim_handle());
+  h->cfg = *cfg;
+  (void)hipGetDevice(&h->device);
+  create_params(h.get());
+  if ((rc = create_alloc(h.get())) != SIM_OK) return rc;
+  if (h->d.rfan && (rc = create_rf(h.get())) != SIM_OK) return rc;
+  if ((rc = create_state(h.get())) != SIM_OK) return rc;
+  *out = h.release();
   return SIM_OK;
 }
 
@@ -352,7 +321,7 @@ static int ensure_slot(sim_handle* h, u32 subject) {
   u32 a = 0;
   while (a < d.A && h->subject_of[a] != NOSLOT) ++a;  // the lowest free slot
   if (a == d.A) return SIM_ENOSLOT;
-  if (int rc = lazy_need(h, h->lz_view, (u64)a + 1)) return rc;  // the slot's plane gets its memory now
+  if (int rc = lazy_need(h, h->sp[SP_VIEW].lz, (u64)a + 1)) return rc;  // the slot's plane gets its memory now
   if (a >= h->n_slots) h->n_slots = a + 1;
   h->n_alloc++;
   h->slot_of[subject] = a;
@@ -815,7 +784,7 @@ int sim_pp_plan(sim_handle* h, uint32_t* send1, uint32_t* recv1, size_t* record_
     all.insert(all.end(), h->pp_s1.begin(), h->pp_s1.end());
     HCHECK(hipMemcpy(h->d_pp, all.data(), tot * 4, hipMemcpyHostToDevice));
   }
-  *record_bytes = (2 + (size_t)tp.n_slots + 2 * (size_t)(d.X + d.Bev)) * 16;
+  *record_bytes = (2 + (size_t)tp.n_slots + 2 * (size_t)h->sp[SP_EV].planes) * 16;
   return SIM_OK;
 }
 int sim_pp_export(sim_handle* h, int round, void* send) {
@@ -828,7 +797,7 @@ int sim_pp_export(sim_handle* h, int round, void* send) {
   u32 n = (u32)(round == 1 ? h->pp_s1.size() : h->pp_r1.size());
   if (!n) return SIM_OK;
   if (!send) return SIM_EINVAL;
-  size_t rec_u4 = 2 + (size_t)tp.n_slots + 2 * (size_t)(d.X + d.Bev);
+  size_t rec_u4 = 2 + (size_t)tp.n_slots + 2 * (size_t)h->sp[SP_EV].planes;
   pp_export_kernel<<<n, 256, 0, h->stream>>>(d, list, tp.n_slots, (uint4*)send, rec_u4);
   HCHECK(hipGetLastError());
   return SIM_OK;
@@ -839,7 +808,7 @@ int sim_pp_merge(sim_handle* h, int round, const void* recv) {
   Dev& d = h->d;
   const TickP& tp = h->cur_tp;
   size_t nl = h->pp_local_a.size();
-  size_t rec_u4 = 2 + (size_t)tp.n_slots + 2 * (size_t)(d.X + d.Bev);
+  size_t rec_u4 = 2 + (size_t)tp.n_slots + 2 * (size_t)h->sp[SP_EV].planes;
   if (round == 1) {
     if (nl) pp_local_kernel<<<(unsigned)((nl + 63) / 64), 64, 0, h->stream>>>(d, tp, h->d_pp, h->d_pp + nl, (u32)nl);
     u32 n = (u32)h->pp_r1.size();
@@ -1045,14 +1014,14 @@ int sim_step_begin(sim_handle* h) {
   if (!d.sharded && h->pp_step && h->tick > 0 && h->tick % h->pp_step == 0) {  // (sharded: the host runs the batch, sim_pp_*)
     u32 cls = (u32)((h->tick / h->pp_step) % PP_GROUPS);
     u32 half = tp.N / 2, n_pairs = half > cls ? (half - cls + PP_GROUPS - 1) / PP_GROUPS : 0;
-    if (n_pairs) pushpull_kernel<<<(n_pairs + 63) / 64, 64, 0, h->stream>>>(d, tp, cls, n_pairs, lazy_mapped(h->lz_ev, d.X + d.Bev) - d.X);
+    if (n_pairs) pushpull_kernel<<<(n_pairs + 63) / 64, 64, 0, h->stream>>>(d, tp, cls, n_pairs, split_mapped(h->sp[SP_EV]) - d.X);
   }
   if (!d.sharded)  // the Reconnector's push-pulls of this tick (none on a batch tick)
     for (size_t i = 0; i < h->rc_a.size(); i += 8) {
       PairBatch pb;
       memset(&pb, 0, sizeof pb);
       for (size_t j = i; j < h->rc_a.size() && j < i + 8; ++j) { pb.a[pb.n] = h->rc_a[j]; pb.b[pb.n++] = h->rc_b[j]; }
-      pp_pairs_kernel<<<1, 64, 0, h->stream>>>(d, tp, pb, lazy_mapped(h->lz_ev, d.X + d.Bev) - d.X);
+      pp_pairs_kernel<<<1, 64, 0, h->stream>>>(d, tp, pb, split_mapped(h->sp[SP_EV]) - d.X);
     }
   // Timing of the tick's launch(es) with HIP events.  One launch per tick: the pair rides on the dispatch itself
   // (hipExtLaunchKernelGGL: start / stop = the kernel's own begin and end, no barrier packets in the stream — two
@@ -1420,14 +1389,12 @@ int sim_state_digest(sim_handle* h, uint64_t out[8]) {
   size_t nw;
   if (cur_inbox(h)) { nw = (size_t)d.fp * d.Nl * (sizeof(sim_packet) / 8); digest_flat<<<grid_for(nw), BLOCK, 0, s>>>((const u64*)cur_inbox(h), nw, h->d_scratch + 2); }
   // (planes without memory are the zeros they stand for: their share of the sum is a function of the word indices alone)
-  auto split = [&](const uint4* arr, size_t tail, const LazyPlanes& L, u32 planes, u64* out) {
-    const size_t have = (size_t)lazy_mapped(L, planes) * d.Nl;
-    if (have) digest_split<<<grid_for(have), BLOCK, 0, s>>>(arr, tail, have, out);
-    if (have < tail) digest_split_zero<<<grid_for(tail - have), BLOCK, 0, s>>>(have, tail, out);
-  };
-  split(d.view, d.vtail, h->lz_view, d.A, h->d_scratch + 3);
-  split(d.ering0, d.etail, h->lz_ev, d.X + d.Bev, h->d_scratch + 4);
-  split(d.qring0, d.qtail, h->lz_q, d.X + d.Bq, h->d_scratch + 5);
+  for (int i = 0; i < SP_N; ++i) {  // words 3, 4, 5: view, event ring, query ring
+    const SplitArr& A = h->sp[i];
+    const size_t have = (size_t)split_mapped(A) * d.Nl;
+    if (have) digest_split<<<grid_for(have), BLOCK, 0, s>>>(A.base, A.tail, have, h->d_scratch + 3 + i);
+    if (have < A.tail) digest_split_zero<<<grid_for(A.tail - have), BLOCK, 0, s>>>(have, A.tail, h->d_scratch + 3 + i);
+  }
   digest_aux<<<grid_for((size_t)d.N + d.N / 32 + 1), BLOCK, 0, s>>>(d.slot_of, d.upmap, d.N, h->d_scratch + 6);
   nw = (size_t)SIM_QT * 2 * (((size_t)d.N + 31) / 32);
   digest_queries<<<grid_for(nw + 2 * SIM_QT + SIM_QT * SIM_QF_WORDS + d.N), BLOCK, 0, s>>>(d.qtab, d.qbits, nw, d.N, h->d_scratch + 7);
@@ -1438,30 +1405,28 @@ int sim_state_digest(sim_handle* h, uint64_t out[8]) {
 }
 
 // Split arrays (view, rings) <-> their canonical interleaved form, in chunks of at most 64 MiB of device scratch
-// (`have`: the entries that have memory — LazyPlanes; the rest of a download is zeros, the rest of an upload is not sent: the
-// caller has seen to it that it is zeros)
-static int split_copy(sim_handle* h, uint4* arr, size_t tail, size_t n_all, size_t have, void* host, bool download) {
+// (only the planes that have memory — LazyPlanes — are copied; the rest of a download is zeros, the rest of an upload is not sent:
+// the caller has seen to it that it is zeros)
+static_assert(sizeof(sim_view) == 32 && sizeof(sim_bucket) == 32, "an entry of a split array: two 16-byte halves");
+static int split_copy(sim_handle* h, const SplitArr& A, void* host, bool download) {
   const size_t CH = (size_t)1 << 21;  // entries per chunk
-  if (download && have < n_all) memset((uint8_t*)host + have * 32, 0, (n_all - have) * 32);
-  const size_t n_entries = std::min(have, n_all);
+  const size_t n_entries = (size_t)split_mapped(A) * h->d.Nl;
+  if (download && n_entries < A.tail) memset((uint8_t*)host + n_entries * 32, 0, (A.tail - n_entries) * 32);
   if (!n_entries) return SIM_OK;
-  uint4* tmp = nullptr;
-  if (hipMalloc((void**)&tmp, std::min(n_entries, CH) * 32) != hipSuccess) return SIM_ENOMEM;
-  hipError_t e = hipSuccess;
-  for (size_t first = 0; first < n_entries && e == hipSuccess; first += CH) {
+  DevScratch<uint4> tmp;  // 2 x 16 bytes an entry
+  if (int rc = tmp.alloc(std::min(n_entries, CH) * 2)) return rc;
+  for (size_t first = 0; first < n_entries; first += CH) {
     size_t cnt = std::min(CH, n_entries - first);
     uint8_t* hp = (uint8_t*)host + first * 32;
     if (download) {
-      canon_entries_kernel<<<grid_for(cnt), BLOCK, 0, h->stream>>>(arr, tail, first, cnt, tmp);
-      e = hipMemcpyAsync(hp, tmp, cnt * 32, hipMemcpyDeviceToHost, h->stream);
+      canon_entries_kernel<<<grid_for(cnt), BLOCK, 0, h->stream>>>(A.base, A.tail, first, cnt, tmp.get());
+      HCHECK(hipMemcpyAsync(hp, tmp.get(), cnt * 32, hipMemcpyDeviceToHost, h->stream));
     } else {
-      e = hipMemcpyAsync(tmp, hp, cnt * 32, hipMemcpyHostToDevice, h->stream);
-      if (e == hipSuccess) uncanon_entries_kernel<<<grid_for(cnt), BLOCK, 0, h->stream>>>(arr, tail, first, cnt, tmp);
+      HCHECK(hipMemcpyAsync(tmp.get(), hp, cnt * 32, hipMemcpyHostToDevice, h->stream));
+      uncanon_entries_kernel<<<grid_for(cnt), BLOCK, 0, h->stream>>>(A.base, A.tail, first, cnt, tmp.get());
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // tmp is reused by the next chunk
+    HCHECK(hipStreamSynchronize(h->stream));  // tmp is reused by the next chunk (and freed behind the last)
   }
-  (void)hipFree(tmp);
-  HCHECK(e);
   return SIM_OK;
 }
 int sim_dump_state(sim_handle* h, uint32_t which, void* buf, size_t cap, size_t* bytes) {
@@ -1473,9 +1438,7 @@ int sim_dump_state(sim_handle* h, uint32_t which, void* buf, size_t cap, size_t*
     case SIM_ARR_ROWS: n = Nl * sizeof(sim_row); break;
     case SIM_ARR_QUEUE: n = Nl * SIM_Q * sizeof(sim_record); break;
     case SIM_ARR_INBOX: src = cur_inbox(h); n = (size_t)d.fp * Nl * sizeof(sim_packet); break;
-    case SIM_ARR_VIEW: src = d.view; n = (size_t)d.A * Nl * sizeof(sim_view); break;
-    case SIM_ARR_ERING: src = d.ering0; n = (size_t)(d.X + d.Bev) * Nl * sizeof(sim_bucket); break;
-    case SIM_ARR_QRING: src = d.qring0; n = (size_t)(d.X + d.Bq) * Nl * sizeof(sim_bucket); break;
+    case SIM_ARR_VIEW: case SIM_ARR_ERING: case SIM_ARR_QRING: n = h->sp[which - SIM_ARR_VIEW].tail * 32; break;
     case SIM_ARR_SLOTMAP: src = d.slot_of; n = (size_t)d.N * 4; break;
     default: return SIM_EINVAL;
   }
@@ -1484,20 +1447,16 @@ int sim_dump_state(sim_handle* h, uint32_t which, void* buf, size_t cap, size_t*
   if (cap < n) return SIM_ERANGE;
   HCHECK(hipStreamSynchronize(h->stream));
   if (which == SIM_ARR_ROWS || which == SIM_ARR_QUEUE) {  // canonical form is assembled on the device
-    void* tmp = nullptr;
-    if (hipMalloc(&tmp, std::max<size_t>(n, 16)) != hipSuccess) return SIM_ENOMEM;
-    if (which == SIM_ARR_ROWS) canon_rows_kernel<<<grid_for(Nl), BLOCK, 0, h->stream>>>(d, (u64*)tmp);
-    else canon_queue_kernel<<<grid_for(Nl), BLOCK, 0, h->stream>>>(d, (uint4*)tmp);
+    DevScratch<uint8_t> tmp;
+    if (int rc = tmp.alloc(n)) return rc;
+    if (which == SIM_ARR_ROWS) canon_rows_kernel<<<grid_for(Nl), BLOCK, 0, h->stream>>>(d, (u64*)tmp.get());
+    else canon_queue_kernel<<<grid_for(Nl), BLOCK, 0, h->stream>>>(d, (uint4*)tmp.get());
     // copy on the handle's stream: a non-blocking stream does not order against the null stream
-    hipError_t e = hipMemcpyAsync(buf, tmp, n, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(tmp);
-    HCHECK(e);
+    HCHECK(hipMemcpyAsync(buf, tmp.get(), n, hipMemcpyDeviceToHost, h->stream));
+    HCHECK(hipStreamSynchronize(h->stream));
     return SIM_OK;
   }
-  if (which == SIM_ARR_VIEW) return split_copy(h, d.view, d.vtail, d.vtail, (size_t)lazy_mapped(h->lz_view, d.A) * Nl, buf, true);
-  if (which == SIM_ARR_ERING) return split_copy(h, d.ering0, d.etail, d.etail, (size_t)lazy_mapped(h->lz_ev, d.X + d.Bev) * Nl, buf, true);
-  if (which == SIM_ARR_QRING) return split_copy(h, d.qring0, d.qtail, d.qtail, (size_t)lazy_mapped(h->lz_q, d.X + d.Bq) * Nl, buf, true);
+  if (which >= SIM_ARR_VIEW && which <= SIM_ARR_QRING) return split_copy(h, h->sp[which - SIM_ARR_VIEW], buf, true);
   if (!src) { memset(buf, 0, n); return SIM_OK; }
   HCHECK(hipMemcpyAsync(buf, src, n, hipMemcpyDeviceToHost, h->stream));
   HCHECK(hipStreamSynchronize(h->stream));
@@ -1506,10 +1465,9 @@ int sim_dump_state(sim_handle* h, uint32_t which, void* buf, size_t cap, size_t*
 
 // (LazyPlanes: the caller may ask about a Lamport time nobody has used yet — its ring plane gets memory, the bucket is empty)
 static int conv_plane(sim_handle* h, u32 kind, u64 ltime) {
-  const Dev& d = h->d;
-  if (kind == SIM_K_EVENT) return lazy_need(h, h->lz_ev, (u64)d.X + (u64)(d.bev_mask ? (u32)ltime & d.bev_mask : (u32)(ltime % d.Bev)) + 1);
-  if (kind == SIM_K_QUERY) return lazy_need(h, h->lz_q, (u64)d.X + (u64)(d.bq_mask ? (u32)ltime & d.bq_mask : (u32)(ltime % d.Bq)) + 1);
-  return SIM_OK;
+  if (kind != SIM_K_EVENT && kind != SIM_K_QUERY) return SIM_OK;
+  SplitArr& A = h->sp[kind == SIM_K_EVENT ? SP_EV : SP_Q];
+  return lazy_need(h, A.lz, (u64)h->d.X + ltime % (A.planes - h->d.X) + 1);  // (bucket t mod B is row X + t mod B)
 }
 // one pass of convergence_many_kernel: dev[0 .. cs.n] zeroed, counted into, copied to r[0 .. cs.n]; returns with the stream idle
 static int conv_run(sim_handle* h, const ConvSet& cs, u64* dev, u64* r) {
@@ -1613,12 +1571,10 @@ int sim_convergence_many(sim_handle* h, uint32_t n, const uint32_t* kinds, const
     cs.n++;
     if (int lrc = conv_plane(h, kinds[i], ltimes[i])) return lrc;
   }
-  u64* scr = nullptr;
-  if (hipMalloc((void**)&scr, (SIM_CONV_MAX + 1) * 8) != hipSuccess) return SIM_ENOMEM;
+  DevScratch<u64> scr;
+  if (int rc = scr.alloc(SIM_CONV_MAX + 1)) return rc;
   u64 r[SIM_CONV_MAX + 1];
-  const int rc = conv_run(h, cs, scr, r);
-  (void)hipFree(scr);
-  if (rc) return rc;
+  if (int rc = conv_run(h, cs, scr.get(), r)) return rc;  // (returns with the stream idle)
   *up = r[0];
   for (u32 i = 0; i < n; ++i) seen[i] = at[i] == ~0u ? 0 : r[1 + at[i]];
   return SIM_OK;
@@ -1633,17 +1589,36 @@ struct snap_header {
   uint64_t ops_dropped, slots_recycled;
 };
 #define SNAP_MAGIC 0x53465253u
-#define SNAP_SECTIONS 16
-static void snap_lengths(const sim_handle* h, size_t len[SNAP_SECTIONS]) {
+// the image's sections, in the order oracle/serf_oracle.c documents
+enum { SEC_ROWS, SEC_QUEUE, SEC_INBOX, SEC_VIEW, SEC_ERING, SEC_QRING, SEC_SLOT_OF, SEC_SUBJECT_OF, SEC_BASE, SEC_UPMAP, SEC_QTAB, SEC_QBITS,
+       SEC_OPS, SEC_ALLOC_TICK, SEC_QFILT, SEC_TAGS, SNAP_SECTIONS };
+static_assert(SEC_VIEW + SP_Q == SEC_QRING && SEC_VIEW == (int)SIM_ARR_VIEW, "the split arrays' sections follow their descriptors");
+// One section: its length and where it lives.  sim_snapshot takes it from the first of: a sim_dump_state array (`dump` >= 0: canonical
+// form, assembled on the device), the handle's host copy, the device array.  sim_restore copies it to the device array (the dumped ones go
+// back through their own kernels) and, last of all, to the host copy.
+struct SnapSec {
+  size_t len;
+  int dump;
+  void* host;
+  void* dev;
+};
+static void snap_sections(sim_handle* h, size_t n_pending, SnapSec sec[SNAP_SECTIONS]) {
   const Dev& d = h->d;
-  size_t nup = ((size_t)d.N + 31) / 32;
-  size_t n[SNAP_SECTIONS] = {(size_t)d.Nl * sizeof(sim_row), (size_t)d.Nl * SIM_Q * sizeof(sim_record),
-                             (size_t)d.fp * d.Nl * sizeof(sim_packet), (size_t)d.A * d.Nl * sizeof(sim_view),
-                             (size_t)(d.X + d.Bev) * d.Nl * sizeof(sim_bucket), (size_t)(d.X + d.Bq) * d.Nl * sizeof(sim_bucket),
-                             (size_t)d.N * 4, (size_t)d.A * 4, (size_t)d.N * sizeof(sim_view), nup * 4,
-                             (size_t)SIM_QT * 16, (size_t)SIM_QT * 2 * nup * 4, (h->ops.size() - h->op_cursor) * sizeof(OpEnt),
-                             (size_t)d.A * 4, (size_t)SIM_QT * SIM_QF_WORDS * 4, (size_t)d.N};
-  memcpy(len, n, sizeof n);
+  const size_t nup = ((size_t)d.N + 31) / 32;
+  sec[SEC_ROWS] = {(size_t)d.Nl * sizeof(sim_row), SIM_ARR_ROWS, nullptr, nullptr};
+  sec[SEC_QUEUE] = {(size_t)d.Nl * SIM_Q * sizeof(sim_record), SIM_ARR_QUEUE, nullptr, nullptr};
+  sec[SEC_INBOX] = {(size_t)d.fp * d.Nl * sizeof(sim_packet), SIM_ARR_INBOX, nullptr, nullptr};
+  for (int i = 0; i < SP_N; ++i) sec[SEC_VIEW + i] = {h->sp[i].tail * 32, SIM_ARR_VIEW + i, nullptr, nullptr};
+  sec[SEC_SLOT_OF] = {(size_t)d.N * 4, -1, h->slot_of.data(), d.slot_of};
+  sec[SEC_SUBJECT_OF] = {(size_t)d.A * 4, -1, h->subject_of.data(), d.subject_of};
+  sec[SEC_BASE] = {(size_t)d.N * sizeof(sim_view), -1, h->base.data(), h->d_base};
+  sec[SEC_UPMAP] = {nup * 4, -1, nullptr, d.upmap};
+  sec[SEC_QTAB] = {(size_t)SIM_QT * 16, -1, nullptr, d.qtab};
+  sec[SEC_QBITS] = {(size_t)SIM_QT * 2 * nup * 4, -1, nullptr, d.qbits};
+  sec[SEC_OPS] = {n_pending * sizeof(OpEnt), -1, h->ops.data() + h->op_cursor, nullptr};  // (host only; restored through a vector of its own)
+  sec[SEC_ALLOC_TICK] = {(size_t)d.A * 4, -1, h->alloc_tick.data(), nullptr};
+  sec[SEC_QFILT] = {(size_t)SIM_QT * SIM_QF_WORDS * 4, -1, h->qfilt.data(), QFILT(d)};
+  sec[SEC_TAGS] = {(size_t)d.N, -1, nullptr, TAGCLASS(d)};
 }
 int sim_snapshot(sim_handle* h, void* buf, size_t cap, size_t* bytes) {
   if (!h || !bytes) return SIM_EINVAL;
@@ -1660,9 +1635,10 @@ int sim_snapshot(sim_handle* h, void* buf, size_t cap, size_t* bytes) {
         if ((rc = inject_val(h, h->tick + 2 - back, SIM_OP_SUSPECT, rq[2 * i], rq[2 * i + 1], 0, 0)) != SIM_OK) return rc;
     }
   }
-  size_t len[SNAP_SECTIONS], tot = sizeof(snap_header);
-  snap_lengths(h, len);
-  for (int i = 0; i < SNAP_SECTIONS; ++i) tot += 8 + len[i];
+  SnapSec sec[SNAP_SECTIONS];
+  snap_sections(h, h->ops.size() - h->op_cursor, sec);
+  size_t tot = sizeof(snap_header);
+  for (const SnapSec& sc : sec) tot += 8 + sc.len;
   *bytes = tot;
   if (!buf) return SIM_OK;
   if (cap < tot) return SIM_ERANGE;
@@ -1674,24 +1650,18 @@ int sim_snapshot(sim_handle* h, void* buf, size_t cap, size_t* bytes) {
   hd.ops_dropped = h->ops_dropped; hd.slots_recycled = h->slots_recycled;
   uint8_t* o = (uint8_t*)buf;
   memcpy(o, &hd, sizeof hd); o += sizeof hd;
-  const uint32_t dumps[6] = {SIM_ARR_ROWS, SIM_ARR_QUEUE, SIM_ARR_INBOX, SIM_ARR_VIEW, SIM_ARR_ERING, SIM_ARR_QRING};
-  for (int i = 0; i < SNAP_SECTIONS; ++i) {
-    uint64_t n = len[i];
+  for (const SnapSec& sc : sec) {
+    const uint64_t n = sc.len;
     memcpy(o, &n, 8); o += 8;
-    if (i < 6) {
+    if (sc.dump >= 0) {
       size_t got = 0;
-      int rc = sim_dump_state(h, dumps[i], o, n, &got);
-      if (rc) return rc;
-    } else if (i == 6) memcpy(o, h->slot_of.data(), n);
-    else if (i == 7) memcpy(o, h->subject_of.data(), n);
-    else if (i == 8) memcpy(o, h->base.data(), n);
-    else if (i == 9) { HCHECK(hipMemcpyAsync(o, d.upmap, n, hipMemcpyDeviceToHost, h->stream)); HCHECK(hipStreamSynchronize(h->stream)); }
-    else if (i == 10) { HCHECK(hipMemcpyAsync(o, d.qtab, n, hipMemcpyDeviceToHost, h->stream)); HCHECK(hipStreamSynchronize(h->stream)); }
-    else if (i == 11) { HCHECK(hipMemcpyAsync(o, d.qbits, n, hipMemcpyDeviceToHost, h->stream)); HCHECK(hipStreamSynchronize(h->stream)); }
-    else if (i == 12) { if (n) memcpy(o, h->ops.data() + h->op_cursor, n); }
-    else if (i == 13) memcpy(o, h->alloc_tick.data(), n);
-    else if (i == 14) memcpy(o, h->qfilt.data(), n);
-    else { HCHECK(hipMemcpyAsync(o, TAGCLASS(d), n, hipMemcpyDeviceToHost, h->stream)); HCHECK(hipStreamSynchronize(h->stream)); }
+      if (int rc = sim_dump_state(h, (uint32_t)sc.dump, o, n, &got)) return rc;
+    } else if (sc.host) {
+      if (n) memcpy(o, sc.host, n);
+    } else {
+      HCHECK(hipMemcpyAsync(o, sc.dev, n, hipMemcpyDeviceToHost, h->stream));
+      HCHECK(hipStreamSynchronize(h->stream));
+    }
     o += n;
   }
   return SIM_OK;
@@ -1703,13 +1673,12 @@ int sim_restore(sim_handle* h, const void* buf, size_t bytes) {
   snap_header hd;
   memcpy(&hd, buf, sizeof hd);
   if (hd.magic != SNAP_MAGIC || hd.abi != SIM_ABI_VERSION || memcmp(&hd.cfg, &h->cfg, sizeof(sim_config))) return SIM_EINVAL;
-  // ---- pass 1: validate the header and every section length before anything is touched ----
+  // ---- pass 1: validate the header, every section length and what the kernels index with, before anything is touched ----
   if (hd.n_slots > d.A) return SIM_EINVAL;                          // reap_run / pp_merge walk a < n_slots
   if ((size_t)hd.n_pending_ops > bytes / sizeof(OpEnt)) return SIM_EINVAL;  // sizes a host allocation
-  size_t len[SNAP_SECTIONS];
-  snap_lengths(h, len);
-  len[12] = (size_t)hd.n_pending_ops * sizeof(OpEnt);
-  const uint8_t* sec[SNAP_SECTIONS];
+  SnapSec sec[SNAP_SECTIONS];
+  snap_sections(h, hd.n_pending_ops, sec);
+  const uint8_t* img[SNAP_SECTIONS];
   {
     const uint8_t* in = (const uint8_t*)buf + sizeof hd;
     const uint8_t* end = (const uint8_t*)buf + bytes;
@@ -1717,124 +1686,109 @@ int sim_restore(sim_handle* h, const void* buf, size_t bytes) {
       uint64_t n;
       if ((size_t)(end - in) < 8) return SIM_EINVAL;
       memcpy(&n, in, 8); in += 8;
-      if (n != len[i] || (size_t)(end - in) < n) return SIM_EINVAL;
-      sec[i] = in;
+      if (n != sec[i].len || (size_t)(end - in) < n) return SIM_EINVAL;
+      img[i] = in;
       in += n;
     }
   }
   uint4* inbox_dst = (d.sharded && !d.rfan) ? h->rbuf[(hd.tick + 1) & 1] : h->inbox_mat;
-  if ((len[2] && !inbox_dst) || (d.sharded && d.rfan && !h->bound)) return SIM_ESTATE;  // sharded: bind the exchange buffers first
+  if ((sec[SEC_INBOX].len && !inbox_dst) || (d.sharded && d.rfan && !h->bound)) return SIM_ESTATE;  // sharded: bind the exchange buffers first
   {  // slot maps must be consistent with n_slots (they index the view) and with each other (the recycling scan and
      // ensure_slot go from a slot to its subject and back)
-    const u32* so = (const u32*)sec[6];
-    const u32* sj = (const u32*)sec[7];
+    const u32* so = (const u32*)img[SEC_SLOT_OF];
+    const u32* sj = (const u32*)img[SEC_SUBJECT_OF];
     for (u32 i = 0; i < d.N; ++i)
       if (so[i] != NOSLOT && (so[i] >= (h->dense ? d.A : hd.n_slots) || sj[so[i]] != i)) return SIM_EINVAL;
     for (u32 a = 0; a < d.A; ++a)
       if (sj[a] != NOSLOT && (sj[a] >= d.N || so[sj[a]] != a)) return SIM_EINVAL;
   }
-  {  // the pending schedule goes straight to ops_kernel: the same checks sim_inject applies
-    const OpEnt* po = (const OpEnt*)sec[12];
-    for (u32 i = 0; i < hd.n_pending_ops; ++i) {
-      OpEnt e;
-      memcpy(&e, po + i, sizeof e);
-      if (op_validate(d.N, e.op, e.node, e.a, e.b) != SIM_OK) return SIM_EINVAL;
-    }
-  }
-  for (u32 j = 0; j < SIM_QT; ++j)  // the kernel loops over n_ids and shifts by the class
-    if (((const u32*)sec[14])[(size_t)j * SIM_QF_WORDS + 1] > SIM_QF_IDS) return SIM_EINVAL;
-  for (u32 i = 0; i < d.N; ++i)
-    if (sec[15][i] >= SIM_TAG_CLASSES) return SIM_EINVAL;
-  // ---- pass 2: device copies (the handle's host state is committed only after they succeed) ----
-  hipStream_t s = h->stream;
-  void* tmp_rows = nullptr;
-  void* tmp_queue = nullptr;
-  int rc = SIM_OK;
-#define RCHECK(x) do { if (rc == SIM_OK && (x) != hipSuccess) rc = SIM_EDEVICE; } while (0)
-  if (hipMalloc(&tmp_rows, std::max<size_t>(len[0], 16)) != hipSuccess) rc = SIM_ENOMEM;
-  if (rc == SIM_OK && hipMalloc(&tmp_queue, std::max<size_t>(len[1], 16)) != hipSuccess) rc = SIM_ENOMEM;
-  auto up = [&](void* dst, int i) { if (len[i]) RCHECK(hipMemcpyAsync(dst, sec[i], len[i], hipMemcpyHostToDevice, s)); };
-  if (rc == SIM_OK) {
-    up(tmp_rows, 0); up(tmp_queue, 1); up(inbox_dst, 2);
-    // (LazyPlanes: memory for the planes the image has anything in; what is mapped beyond them is overwritten with the image's zeros)
-    // (`least`: planes that need memory whatever the image holds — a slot that was handed out may hold nothing but zeros)
-    auto up_split = [&](uint4* arr, size_t tail, LazyPlanes& L, u32 planes, const uint8_t* img, u32 least) {
-      if (rc != SIM_OK) return;
-      if (L.va) {
-        const size_t pb = (size_t)d.Nl * 32;
-        u32 used = planes;
-        while (used > 0) {  // the last plane with a non-zero byte
-          const uint8_t* p = img + (size_t)(used - 1) * pb;
-          if (p[0] || memcmp(p, p + 1, pb - 1)) break;
-          --used;
-        }
-        rc = lazy_need(h, L, std::max(used, least));
-      }
-      if (rc == SIM_OK) rc = split_copy(h, arr, tail, tail, (size_t)lazy_mapped(L, planes) * d.Nl, (void*)img, false);
-    };
-    up_split(d.view, d.vtail, h->lz_view, d.A, sec[3], hd.n_slots);
-    up_split(d.ering0, d.etail, h->lz_ev, d.X + d.Bev, sec[4], 0);
-    up_split(d.qring0, d.qtail, h->lz_q, d.X + d.Bq, sec[5], 0);
-    up(d.slot_of, 6); up(d.subject_of, 7); up(h->d_base, 8); up(d.upmap, 9); up(d.qtab, 10); up(d.qbits, 11);
-    up(QFILT(d), 14); up(TAGCLASS(d), 15);
-    // canonical rows / queue -> packed row groups, sort keys + slot-stable payloads
-    RCHECK(hipMemsetAsync(d.R2, 0, (size_t)d.Nl * 16, s));
-    if (rc == SIM_OK) {
-      restore_queue_kernel<<<grid_for(d.Nl), BLOCK, 0, s>>>(d, (const uint4*)tmp_queue);
-      restore_rows_kernel<<<grid_for(d.Nl), BLOCK, 0, s>>>(d, (const u64*)tmp_rows);
-      if (!d.sharded || d.rfan) {  // the packets in flight go back to their senders (one cell per slot)
-        TickP p;
-        tickp_make(&p, &h->cfg, hd.tick ? hd.tick - 1 : 0);
-        // (random fan-out: back to their places in their targets' rows — the graph of the tick they were sent in is a
-        // function of (seed, tick) and is built again first)
-        // (random fan-out: the graph of the packets in flight is a function of (seed, tick - 1): sim_step_begin builds it again)
-        unmaterialize_kernel<<<grid_for(d.Nl), BLOCK, 0, s>>>(d, p, (u32)(hd.tick & 1), hd.tick ? 1u : 0u, h->inbox_mat);
-      }
-      RCHECK(hipGetLastError());
-    }
-    RCHECK(hipStreamSynchronize(s));
-  }
-#undef RCHECK
-  if (tmp_rows) (void)hipFree(tmp_rows);
-  if (tmp_queue) (void)hipFree(tmp_queue);
-  if (rc != SIM_OK) return rc;
-  // (ADVICE r5) everything that can still fail comes BEFORE the first host field is committed: the pending schedule is parsed into
-  // a vector of its own, the bounds on the clocks are worked out from the image and the ring planes they need are mapped now
+  // the pending schedule goes straight to ops_kernel: the same checks sim_inject applies (parsed into a vector of its own)
   std::vector<OpEnt> new_ops(hd.n_pending_ops, OpEnt{0, 0, 0, 0, 0});
-  if (len[12]) memcpy(new_ops.data(), sec[12], len[12]);
-  if (h->lz_ev.va || h->lz_q.va) {  // LazyPlanes: the bounds on the clocks from the image — the rows' clocks, what the pending operations add
+  if (sec[SEC_OPS].len) memcpy(new_ops.data(), img[SEC_OPS], sec[SEC_OPS].len);
+  for (const OpEnt& e : new_ops)
+    if (op_validate(d.N, e.op, e.node, e.a, e.b) != SIM_OK) return SIM_EINVAL;
+  for (u32 j = 0; j < SIM_QT; ++j)  // the kernel loops over n_ids and shifts by the class
+    if (((const u32*)img[SEC_QFILT])[(size_t)j * SIM_QF_WORDS + 1] > SIM_QF_IDS) return SIM_EINVAL;
+  for (u32 i = 0; i < d.N; ++i)
+    if (img[SEC_TAGS][i] >= SIM_TAG_CLASSES) return SIM_EINVAL;
+  // ---- pass 2: everything that can fail for lack of memory, before the first byte of the image reaches the device (ADVICE r5, r6) ----
+  hipStream_t s = h->stream;
+  DevScratch<uint8_t> tmp_rows, tmp_queue;
+  if (int rc = tmp_rows.alloc(sec[SEC_ROWS].len)) return rc;
+  if (int rc = tmp_queue.alloc(sec[SEC_QUEUE].len)) return rc;
+  {
+    // LazyPlanes: memory for the planes the image has anything in (what is mapped beyond them is overwritten with the image's zeros) and
+    // for the planes that need it whatever the image holds — a slot that was handed out may hold nothing but zeros
+    u64 need[SP_N] = {hd.n_slots, 0, 0};
+    for (int i = 0; i < SP_N; ++i) {
+      if (!h->sp[i].lz.va) continue;
+      const size_t pb = (size_t)d.Nl * 32;
+      u32 used = h->sp[i].planes;
+      while (used > 0) {  // the last plane with a non-zero byte
+        const uint8_t* p = img[SEC_VIEW + i] + (size_t)(used - 1) * pb;
+        if (p[0] || memcmp(p, p + 1, pb - 1)) break;
+        --used;
+      }
+      need[i] = std::max<u64>(need[i], used);
+    }
+    // ... and the bounds on the clocks from the image — the rows' clocks, what the pending operations add — with the ring planes they need
     u64 eh = 1, qh = 1;
-    for (size_t i = 0; i < d.Nl; ++i) {
-      sim_row r;
-      memcpy(&r, sec[0] + i * sizeof(sim_row), sizeof r);
-      eh = std::max(eh, r.event_clock); qh = std::max(qh, r.query_clock);
+    if (h->sp[SP_EV].lz.va || h->sp[SP_Q].lz.va) {
+      for (size_t i = 0; i < d.Nl; ++i) {
+        sim_row r;
+        memcpy(&r, img[SEC_ROWS] + i * sizeof(sim_row), sizeof r);
+        eh = std::max(eh, r.event_clock); qh = std::max(qh, r.query_clock);
+      }
+      for (const OpEnt& e : new_ops) {
+        const u64 t1 = std::min<u64>(e.val, ~0ull - 4) + 1;
+        if (e.op == SIM_OP_USER_EVENT) ++eh;
+        else if (e.op == SIM_OP_QUERY) ++qh;
+        else if ((e.op == SIM_OP_DELIVER && SIM_META_KIND(e.b) == SIM_K_EVENT) || (e.op == SIM_OP_WITNESS && e.a == 1u)) eh = std::max(eh, t1);
+        else if ((e.op == SIM_OP_DELIVER && SIM_META_KIND(e.b) == SIM_K_QUERY) || (e.op == SIM_OP_WITNESS && e.a == 2u)) qh = std::max(qh, t1);
+      }
+      // (a pending event originates at a clock <= the maximum so far; its witnesses end one above it)
     }
-    for (const OpEnt& e : new_ops) {
-      const u64 t1 = std::min<u64>(e.val, ~0ull - 4) + 1;
-      if (e.op == SIM_OP_USER_EVENT) ++eh;
-      else if (e.op == SIM_OP_QUERY) ++qh;
-      else if ((e.op == SIM_OP_DELIVER && SIM_META_KIND(e.b) == SIM_K_EVENT) || (e.op == SIM_OP_WITNESS && e.a == 1u)) eh = std::max(eh, t1);
-      else if ((e.op == SIM_OP_DELIVER && SIM_META_KIND(e.b) == SIM_K_QUERY) || (e.op == SIM_OP_WITNESS && e.a == 2u)) qh = std::max(qh, t1);
-    }
-    // (a pending event originates at a clock <= the maximum so far; its witnesses end one above it)
     const u64 eh0 = h->ev_hi, qh0 = h->q_hi;
-    h->ev_hi = eh; h->q_hi = qh;
-    if (int lrc = rings_need(h)) { h->ev_hi = eh0; h->q_hi = qh0; return lrc; }  // the handle is still the fresh one it was
+    h->ev_hi = std::max(eh, eh0); h->q_hi = std::max(qh, qh0);
+    int lrc = SIM_OK;
+    for (int i = 0; i < SP_N && lrc == SIM_OK; ++i) lrc = lazy_need(h, h->sp[i].lz, need[i]);
+    if (lrc == SIM_OK) lrc = rings_need(h);
+    if (lrc) { h->ev_hi = eh0; h->q_hi = qh0; return lrc; }  // the handle is still the fresh one it was (with some planes more, all zeros)
   }
+  // ---- pass 3: device copies, behind the planes' memsets (the handle's host state is committed only after they succeed) ----
+  auto up = [&](void* dst, int i) { return sec[i].len ? hipMemcpyAsync(dst, img[i], sec[i].len, hipMemcpyHostToDevice, s) : hipSuccess; };
+  HCHECK(up(tmp_rows.get(), SEC_ROWS)); HCHECK(up(tmp_queue.get(), SEC_QUEUE)); HCHECK(up(inbox_dst, SEC_INBOX));
+  for (int i = 0; i < SP_N; ++i)
+    if (int rc = split_copy(h, h->sp[i], (void*)img[SEC_VIEW + i], false)) return rc;
+  for (int i = SEC_SLOT_OF; i < SNAP_SECTIONS; ++i)
+    if (sec[i].dev) HCHECK(up(sec[i].dev, i));
+  // canonical rows / queue -> packed row groups, sort keys + slot-stable payloads
+  HCHECK(hipMemsetAsync(d.R2, 0, (size_t)d.Nl * 16, s));
+  restore_queue_kernel<<<grid_for(d.Nl), BLOCK, 0, s>>>(d, (const uint4*)tmp_queue.get());
+  restore_rows_kernel<<<grid_for(d.Nl), BLOCK, 0, s>>>(d, (const u64*)tmp_rows.get());
+  if (!d.sharded || d.rfan) {  // the packets in flight go back to their senders (one cell per slot)
+    TickP p;
+    tickp_make(&p, &h->cfg, hd.tick ? hd.tick - 1 : 0);
+    // (random fan-out: the graph of the packets in flight is a function of (seed, tick - 1): sim_step_begin builds it again)
+    unmaterialize_kernel<<<grid_for(d.Nl), BLOCK, 0, s>>>(d, p, (u32)(hd.tick & 1), hd.tick ? 1u : 0u, h->inbox_mat);
+  }
+  HCHECK(hipGetLastError());
+  HCHECK(hipStreamSynchronize(s));  // (the scratch goes after this)
+  // ---- the host state ----
   h->tick = hd.tick;
   h->mat_tick = (d.sharded && !d.rfan) ? ~0ull : hd.tick;  // the image's inbox section is what sits in inbox_mat
   h->n_slots = hd.n_slots;
   if (hd.tick > 0) tickp_make(&h->prev, &h->cfg, hd.tick - 1);  // the parameters the packets in flight were sent with
-  memcpy(h->slot_of.data(), sec[6], len[6]);
-  memcpy(h->subject_of.data(), sec[7], len[7]);
-  memcpy(h->base.data(), sec[8], len[8]);
+  memcpy(h->slot_of.data(), img[SEC_SLOT_OF], sec[SEC_SLOT_OF].len);
+  memcpy(h->subject_of.data(), img[SEC_SUBJECT_OF], sec[SEC_SUBJECT_OF].len);
+  memcpy(h->base.data(), img[SEC_BASE], sec[SEC_BASE].len);
   h->walk.clear();
   for (u32 subj = 0; subj < d.N; ++subj)
     if (h->slot_of[subj] != NOSLOT) h->walk.push_back(h->slot_of[subj]);
   if (!h->walk.empty()) HCHECK(hipMemcpy(d.walk, h->walk.data(), h->walk.size() * 4, hipMemcpyHostToDevice));
   h->ops.swap(new_ops);
-  memcpy(h->alloc_tick.data(), sec[13], len[13]);
-  memcpy(h->qfilt.data(), sec[14], len[14]);
+  memcpy(h->alloc_tick.data(), img[SEC_ALLOC_TICK], sec[SEC_ALLOC_TICK].len);
+  memcpy(h->qfilt.data(), img[SEC_QFILT], sec[SEC_QFILT].len);
   h->n_alloc = (u32)h->walk.size();
   h->ops_dropped = hd.ops_dropped; h->slots_recycled = hd.slots_recycled;
   h->recycle_at = 0xFFFFFFFFu;
@@ -1899,23 +1853,6 @@ int sim_profile(sim_handle* h, int enable) {
   h->prof_seq = 0;
   return SIM_OK;
 }
-int sim_profile_read(sim_handle* h, double* ms, uint64_t* launches) {
-  if (!h || !ms || !launches) return SIM_EINVAL;
-  HCHECK(hipStreamSynchronize(h->stream));
-  double tot = 0.0;
-  for (auto& pr : h->prof) {
-    float t = 0.f;
-    HCHECK(hipEventElapsedTime(&t, pr.first, pr.second));
-    tot += t;
-    (void)hipEventDestroy(pr.first);
-    (void)hipEventDestroy(pr.second);
-  }
-  *ms = tot;
-  *launches = h->prof.size();
-  for (int i = 0; i < 3; ++i) h->sreq_wait[i] = nullptr;  // (the stream was synchronised above: every tick has finished)
-  h->prof.clear();
-  return SIM_OK;
-}
 int sim_profile_read_stats(sim_handle* h, double out_ms[3], uint64_t* launches) {
   if (!h || !out_ms || !launches) return SIM_EINVAL;
   HCHECK(hipStreamSynchronize(h->stream));
@@ -1937,35 +1874,34 @@ int sim_profile_read_stats(sim_handle* h, double out_ms[3], uint64_t* launches) 
   h->prof.clear();
   return SIM_OK;
 }
+int sim_profile_read(sim_handle* h, double* ms, uint64_t* launches) {  // the total alone
+  if (!ms) return SIM_EINVAL;
+  double out_ms[3];
+  const int rc = sim_profile_read_stats(h, out_ms, launches);
+  if (rc == SIM_OK) *ms = out_ms[0];
+  return rc;
+}
 int sim_resident_planes(const sim_handle* h, uint32_t out[6], uint64_t* bytes_per_plane) {
   if (!h || !out) return SIM_EINVAL;
-  const Dev& d = h->d;
-  out[0] = lazy_mapped(h->lz_view, d.A); out[1] = d.A;
-  out[2] = lazy_mapped(h->lz_ev, d.X + d.Bev); out[3] = d.X + d.Bev;
-  out[4] = lazy_mapped(h->lz_q, d.X + d.Bq); out[5] = d.X + d.Bq;
-  if (bytes_per_plane) *bytes_per_plane = (uint64_t)d.Nl * 32;
+  for (int i = 0; i < SP_N; ++i) { out[2 * i] = split_mapped(h->sp[i]); out[2 * i + 1] = h->sp[i].planes; }
+  if (bytes_per_plane) *bytes_per_plane = (uint64_t)h->d.Nl * 32;
   return SIM_OK;
 }
 int sim_cluster_stats_get(sim_handle* h, sim_cluster_stats* out) {
   if (!h || !out) return SIM_EINVAL;
   Dev& d = h->d;
   hipStream_t s = h->stream;
-  u64* scr = nullptr;  // [10] the figures, then [workgroups][10] partial ones
+  DevScratch<u64> scr;  // [10] the figures, then [workgroups][10] partial ones
   const u32 nwg = (u32)std::min<int>(grid_for(d.Nl), CSTAT_WG);
-  if (hipMalloc((void**)&scr, (size_t)(1 + nwg) * 10 * 8) != hipSuccess) return SIM_ENOMEM;
+  if (int rc = scr.alloc((size_t)(1 + nwg) * 10)) return rc;
   u64 r[10];
-  hipError_t e = hipSuccess;
-  {
-    // sharded: the packets in flight sit in the receive buffer, [src][k][blk] = f * Nl cells as well
-    cluster_stats_kernel<<<nwg, BLOCK, 0, s>>>(d, cur_inbox(h), scr + 10);
-    cluster_stats_fold<<<1, dim3(64, 10), 0, s>>>(scr + 10, nwg, scr);
-    e = hipMemcpyAsync(r, scr, sizeof r, hipMemcpyDeviceToHost, s);
-  }
+  // sharded: the packets in flight sit in the receive buffer, [src][k][blk] = f * Nl cells as well
+  cluster_stats_kernel<<<nwg, BLOCK, 0, s>>>(d, cur_inbox(h), scr.get() + 10);
+  cluster_stats_fold<<<1, dim3(64, 10), 0, s>>>(scr.get() + 10, nwg, scr.get());
+  HCHECK(hipMemcpyAsync(r, scr.get(), sizeof r, hipMemcpyDeviceToHost, s));
   u32 evc = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&evc, d.ev_count, 4, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(scr);
-  HCHECK(e);
+  HCHECK(hipMemcpyAsync(&evc, d.ev_count, 4, hipMemcpyDeviceToHost, s));
+  HCHECK(hipStreamSynchronize(s));
   out->up = r[0];
   for (int i = 0; i < 4; ++i) out->queued[i] = r[1 + i];
   out->overflow = r[5]; out->inbox_records = r[6]; out->failed = r[7]; out->left = r[8]; out->max_queue = r[9];

@@ -253,8 +253,8 @@ __global__ __launch_bounds__(BLOCK) void census_pack_kernel(CenDevP p) {
 
 // ---- host ----
 struct CensusState {
-  u64* d_part = nullptr;  // [A][SIM_CENSUS_WORDS][S]
-  u64* d_rec = nullptr;   // [A][SIM_CENSUS_WORDS]
+  DevScratch<u64> d_part;  // [A][SIM_CENSUS_WORDS][S]
+  DevScratch<u64> d_rec;   // [A][SIM_CENSUS_WORDS]
   Sampler smp;            // samples of (1 + maxsub) * SIM_CENSUS_WORDS words
   u32 maxsub = 0;
 };
@@ -262,24 +262,15 @@ static inline u32 census_segments(const sim_handle* h) { return (h->d.Nl + CEN_S
 static inline size_t census_stride(u32 maxsub) { return ((size_t)maxsub + 1u) * SIM_CENSUS_WORDS; }  // words of a sample
 
 // the kernels' scratch, for every slot the handle can ever hand out
-static int census_scratch(const sim_handle* h, u64** part, u64** rec) {
+static int census_scratch(const sim_handle* h, DevScratch<u64>& part, DevScratch<u64>& rec) {
   const u64 cells = (u64)h->d.A * census_segments(h);
-  *part = *rec = nullptr;
   if (cells > 0x7FFFFFFFull) return SIM_ENOMEM;  // (a grid of that many workgroups; its partial records alone would be 256 GiB)
-  if (hipMalloc((void**)part, (size_t)cells * SIM_CENSUS_WORDS * 8) != hipSuccess ||
-      hipMalloc((void**)rec, (size_t)h->d.A * SIM_CENSUS_WORDS * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    if (*part) (void)hipFree(*part);
-    *part = *rec = nullptr;
-    return SIM_ENOMEM;
-  }
-  return SIM_OK;
+  if (int rc = part.alloc((size_t)cells * SIM_CENSUS_WORDS)) return rc;
+  return rec.alloc((size_t)h->d.A * SIM_CENSUS_WORDS);
 }
 static void census_destroy(sim_handle* h) {
   CensusState* s = h->cen;
   if (!s) return;
-  if (s->d_part) (void)hipFree(s->d_part);
-  if (s->d_rec) (void)hipFree(s->d_rec);
   sampler_close(s->smp);
   delete s;
   h->cen = nullptr;
@@ -307,7 +298,7 @@ static int census_step_end(sim_handle* h) {
   CensusState* s = h->cen;
   u64* slot = sampler_slot(h, s->smp);
   if (!slot) return SIM_OK;
-  if (int rc = census_launch(h, s->d_part, s->d_rec, slot, s->maxsub)) return rc;
+  if (int rc = census_launch(h, s->d_part.get(), s->d_rec.get(), slot, s->maxsub)) return rc;
   sampler_commit(s->smp);
   return SIM_OK;
 }
@@ -323,7 +314,7 @@ int sim_census_start(sim_handle* h, uint32_t first_tick, uint32_t period, uint32
   CensusState* s = new CensusState();
   h->cen = s;
   s->maxsub = max_subjects;
-  if (census_scratch(h, &s->d_part, &s->d_rec) != SIM_OK ||
+  if (census_scratch(h, s->d_part, s->d_rec) != SIM_OK ||
       sampler_open(h, s->smp, first_tick, period, capacity, census_stride(max_subjects)) != SIM_OK) {
     (void)hipGetLastError();
     census_destroy(h);
@@ -358,22 +349,17 @@ int sim_census_now(sim_handle* h, sim_census_header* hdr, sim_census_subject* re
   if (int rc = observer_usable(h)) return rc;
   if (!hdr || !n || (cap && !recs)) return SIM_EINVAL;
   const u32 maxsub = std::min(cap, h->d.A);  // (there are no more subjects than slots)
-  u64 *part = nullptr, *rec = nullptr, *out = nullptr;
-  const bool own = !h->cen;  // (a running census lends its scratch: the stream orders the two uses)
-  if (own) {
-    if (int rc = census_scratch(h, &part, &rec)) return rc;
-  } else {
-    part = h->cen->d_part; rec = h->cen->d_rec;
-  }
+  DevScratch<u64> own_part, own_rec, out;
+  // (a running census lends its scratch: the stream orders the two uses)
+  if (!h->cen) { if (int rc = census_scratch(h, own_part, own_rec)) return rc; }
+  u64* part = h->cen ? h->cen->d_part.get() : own_part.get();
+  u64* rec = h->cen ? h->cen->d_rec.get() : own_rec.get();
   std::vector<u64> host(census_stride(maxsub));
-  int rc = SIM_OK;
-  if (hipMalloc((void**)&out, host.size() * 8) != hipSuccess) { (void)hipGetLastError(); out = nullptr; rc = SIM_ENOMEM; }
-  if (rc == SIM_OK) rc = census_launch(h, part, rec, out, maxsub);
+  int rc = out.alloc(host.size());
+  if (rc == SIM_OK) rc = census_launch(h, part, rec, out.get(), maxsub);
   if (hipStreamSynchronize(h->stream) != hipSuccess && rc == SIM_OK) rc = SIM_EDEVICE;  // (also before the scratch goes)
-  if (rc == SIM_OK && hipMemcpy(host.data(), out, host.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = SIM_EDEVICE;
-  if (out) (void)hipFree(out);
-  if (own) { (void)hipFree(part); (void)hipFree(rec); }
   if (rc != SIM_OK) return rc;
+  HCHECK(hipMemcpy(host.data(), out.get(), host.size() * 8, hipMemcpyDeviceToHost));
   memcpy(hdr, host.data(), sizeof *hdr);
   const u32 stored = (u32)host[CH_STORED];
   if (stored) memcpy(recs, host.data() + SIM_CENSUS_WORDS, (size_t)stored * sizeof *recs);

@@ -88,6 +88,7 @@ int sim_exchange_init(sim_handle* h, const uint8_t* id, uint32_t rank, uint32_t 
   if (d.swim && !(xhe && *xhe == '0')) {  // (r6) the suspicion lists' heads travel with the round's exchange: see sim_handle::xh_dev
     const size_t bytes = (size_t)4u * world * SIM_SREQ_HEAD_WORDS * 4u;
     HCHECK(hipMalloc((void**)&h->xh_dev, bytes));
+    h->allocs.push_back(h->xh_dev);
     HCHECK(hipMemsetAsync(h->xh_dev, 0, bytes, h->stream));
     HCHECK(hipHostMalloc((void**)&h->xh_host, bytes, hipHostMallocDefault));
     memset(h->xh_host, 0, bytes);

@@ -25,123 +25,154 @@ struct LazyPlanes {
   std::vector<std::pair<void*, size_t>> maps;               // what is mapped where (to unmap)
   std::vector<hipMemGenericAllocationHandle_t> phys;
 };
+// One of the handle's three split arrays: where it starts, where its tails start (in entries: planes * Nl), how many planes it has and
+// which of them have memory.  The kernels read their own copy (Dev::view / vtail, ering0 / etail, qring0 / qtail), set from these once.
+struct SplitArr {
+  uint4* base = nullptr;
+  size_t tail = 0;
+  u32 planes = 0;
+  LazyPlanes lz;
+};
+enum { SP_VIEW = 0, SP_EV = 1, SP_Q = 2, SP_N = 3 };  // (the order of SIM_ARR_VIEW .. SIM_ARR_QRING and of the image's sections)
+// Function-local device scratch: freed when it goes out of scope — behind whatever stream synchronisation stands before that.
+template <typename T>
+struct DevScratch {
+  T* p = nullptr;
+  DevScratch() = default;
+  DevScratch(DevScratch&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevScratch& operator=(DevScratch&& o) noexcept { std::swap(p, o.p); return *this; }
+  DevScratch(const DevScratch&) = delete;
+  DevScratch& operator=(const DevScratch&) = delete;
+  ~DevScratch() { if (p) (void)hipFree(p); }
+  int alloc(size_t n) {  // n elements (one at least); SIM_ENOMEM
+    if (hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess) return SIM_OK;
+    (void)hipGetLastError();
+    p = nullptr;
+    return SIM_ENOMEM;
+  }
+  T* get() const { return p; }
+};
 struct sim_handle {
-  sim_config cfg;
-  Dev d;
-  u64 tick;
-  u32 dense, n_slots;
-  hipStream_t stream;
+  sim_config cfg = {};
+  Dev d = {};
+  u64 tick = 0;
+  u32 dense = 0, n_slots = 0;
+  hipStream_t stream = nullptr;
   std::vector<u32> slot_of, subject_of;
   std::vector<u32> walk;  // host copy of d.walk
   std::vector<u32> alloc_tick;  // [A] tick at which the slot was handed out
-  u32 n_alloc;                  // slots in use
-  uint8_t* rc_refd;             // the recycling pass's device scratch (the first pass allocates, sim_destroy frees with the rest): [N] "still mentioned",
-  u32* rc_scr;                  // and the candidates' words
-  u64 ops_dropped, slots_recycled;
-  u64 events_lost;              // events the bounded device log dropped (counted when they are drained)
-  u32 recycle_at;               // the tick whose recycling pass has already run
-  u32 pp_done_at;               // the tick whose push-pull batch the sharded host has already run
+  u32 n_alloc = 0;              // slots in use
+  uint8_t* rc_refd = nullptr;   // the recycling pass's device scratch (the first pass allocates, the handle frees with the rest): [N] "still mentioned",
+  u32* rc_scr = nullptr;        // and the candidates' words
+  u64 ops_dropped = 0, slots_recycled = 0;
+  u64 events_lost = 0;          // events the bounded device log dropped (counted when they are drained)
+  u32 recycle_at = 0xFFFFFFFFu; // the tick whose recycling pass has already run
+  u32 pp_done_at = 0xFFFFFFFFu; // the tick whose push-pull batch the sharded host has already run
   // the batch being driven by the sharded host: in-shard pairs, and the cross-shard pairs grouped by peer shard in
   // ascending pair order — r1: this shard owns the even node `a` (receives b in round 1, sends a in round 2); s1: owns `b`
   std::vector<u32> pp_local_a, pp_local_b, pp_r1, pp_s1;
   std::vector<u32> rc_a, rc_b;  // Reconnector: the reconnect attempts that run as push-pull pairs in THIS tick (global ids; initiator, target)
-  u32* d_pp;                    // the four lists on the device, back to back
+  u32* d_pp = nullptr;          // the four lists on the device, back to back (replaced by every sim_pp_plan: not one of `allocs`)
   std::vector<sim_view> base;
-  uint4* d_base;  // [N][2]
+  uint4* d_base = nullptr;  // [N][2]
   std::vector<OpEnt> ops;
-  size_t op_cursor;
-  u64* d_scratch;  // 16 x u64
-  uint8_t* d_mst;
-  u64* d_mlt;
-  sim_stats* d_stats;
-  std::vector<void*> allocs;
-  TickP prev;
-  bool bound;
-  int device;
-  u32 qt_cursor, q_timeout;  // running-query trackers (SIM_QT, round robin); query timeout in ticks
+  size_t op_cursor = 0;
+  u64* d_scratch = nullptr;  // 16 x u64
+  uint8_t* d_mst = nullptr;
+  u64* d_mlt = nullptr;
+  sim_stats* d_stats = nullptr;
+  std::vector<void*> allocs;  // every device allocation that lives as long as the handle
+  TickP prev = {};
+  bool bound = false;
+  int device = 0;
+  u32 qt_cursor = 0, q_timeout = 0;  // running-query trackers (SIM_QT, round robin); query timeout in ticks
   std::vector<u32> qfilt;    // [SIM_QT][SIM_QF_WORDS] host copy of the query filters (the host is their only writer)
   // content of the user events the library was told in bytes (sim_deliver_message, sim_user_event_bytes): what
   // sim_peek_packet encodes for their keys
   std::unordered_map<u32, std::pair<serf::wire::Bytes, serf::wire::Bytes>> evreg;
-  u32 profiling;  // 0 = off, n = HIP events around every n-th tick-kernel launch
-  u64 prof_seq;
+  u32 profiling = 0;  // 0 = off, n = HIP events around every n-th tick-kernel launch
+  u64 prof_seq = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof;  // one event pair per tick-kernel launch
   // slot-less failed probes (SIMSPEC §2.7): device lists by tick parity, their heads copied to pinned host memory behind
   // every tick's launch; the list of tick t is read at the end of tick t + 1 — by then the copy has long landed, nobody
   // waits for a kernel — and replayed as operations of tick t + 2
-  u32* sreq_buf[3];
-  u32* sreq_host[3];       // pinned, written by the kernel itself: the first SREQ_HEAD pairs, unused ones 0xFFFFFFFF
-  hipEvent_t sreq_ev[3];
-  hipEvent_t sreq_wait[3]; // what marks "tick t's kernel has finished": sreq_ev (recorded behind the launch, or riding on the dispatch
-                           // itself as its stop event) or the stop event of the tick's timing pair; null: the stream was synchronised since
-  bool sreq_on_dispatch;   // this tick's launch carried its completion event: sim_step_end records nothing
-  u64 sreq_tick[3];        // the tick whose list sits in the buffer (~0: none / consumed)
-  u32 pp_step;  // push-pull batches: every pp_step ticks one of PP_GROUPS pair classes synchronises (0 = off)
-  TickP cur_tp;            // parameters of the tick between sim_step_begin and sim_step_end
-  bool in_tick, tick_timed, tick_bracket;
-  hipEvent_t tick_ev0;
-  uint4* rbuf[2];          // sharded: packets sent during tick t are received into rbuf[t & 1]
+  u32* sreq_buf[3] = {};
+  u32* sreq_host[3] = {};       // pinned, written by the kernel itself: the first SREQ_HEAD pairs, unused ones 0xFFFFFFFF
+  hipEvent_t sreq_ev[3] = {};
+  hipEvent_t sreq_wait[3] = {}; // what marks "tick t's kernel has finished": sreq_ev (recorded behind the launch, or riding on the dispatch
+                                // itself as its stop event) or the stop event of the tick's timing pair; null: the stream was synchronised since
+  bool sreq_on_dispatch = false;  // this tick's launch carried its completion event: sim_step_end records nothing
+  u64 sreq_tick[3] = {~0ull, ~0ull, ~0ull};  // the tick whose list sits in the buffer (~0: none / consumed)
+  u32 pp_step = 0;  // push-pull batches: every pp_step ticks one of PP_GROUPS pair classes synchronises (0 = off)
+  TickP cur_tp = {};       // parameters of the tick between sim_step_begin and sim_step_end
+  bool in_tick = false, tick_timed = false, tick_bracket = false;
+  hipEvent_t tick_ev0 = nullptr;
+  uint4* rbuf[2] = {};     // sharded: packets sent during tick t are received into rbuf[t & 1]
   // local mode: the packets in flight in their canonical receiver-indexed form inbox[k][node] (what the oracle keeps,
   // what dumps, digests and images hold), produced from Dev::obox on demand; mat_tick = the tick it was made for
-  uint4* inbox_mat;
-  u64 mat_tick;
-  // SIM_CF_RANDOM_FANOUT: scratch of the per-tick graph build (rf_* kernels)
+  uint4* inbox_mat = nullptr;
+  u64 mat_tick = ~0ull;
   // the round's all-to-all over RCCL, issued by the library (sim_exchange_*): the communicator, a stream of its own for the
   // collectives (it waits for one chunk's launch, the handle's stream waits for all of a round's exchanges before the next
   // tick reads them), the events that carry those two orderings
-  ncclComm_t xcomm;
-  hipStream_t xstream;
-  hipEvent_t xev_go, xev_done;
-  u32 xworld;
-  bool xpending;  // exchanges issued since the handle's stream last waited for them
-  bool self_direct;  // packed slabs: the slab this shard addresses to itself is packed straight into the receive buffer and is not exchanged (set by sim_exchange_init)
+  ncclComm_t xcomm = nullptr;
+  hipStream_t xstream = nullptr;
+  hipEvent_t xev_go = nullptr, xev_done = nullptr;
+  u32 xworld = 0;
+  bool xpending = false;  // exchanges issued since the handle's stream last waited for them
+  bool self_direct = false;  // packed slabs: the slab this shard addresses to itself is packed straight into the receive buffer and is not exchanged (set by sim_exchange_init)
   // (r6) the heads of the slot-less suspicion lists travel WITH the round's exchange (SWIM on): every peer's head of tick t lands in
   // xh_dev[t % 4][peer], a small kernel behind the group writes what the lists hold — counts and pairs — into pinned host memory,
   // xh_ev[t % 4] marks it; sim_suspect_import(h, t, NULL, world) reads it two ticks later.  No side stream, no second collective,
   // no copy commands between the pack and the next tick's index pass.
-  u32* xh_dev;             // [4][world][SIM_SREQ_HEAD_WORDS]
-  u32* xh_host;            // pinned, same shape
-  hipEvent_t xh_ev[4];
-  u64 xh_tick[4];          // the tick whose heads slot i holds (~0: none / consumed)
-  u32 *rf_gcur[2];     // bucket fill counters (two: a build zeroes the next one's)
-  void *rf_ovf[2], *rf_l1;  // overflow lists (two, likewise) and the buckets' regions: u32 entries when a pair id and a target's offset fit, u64 otherwise
-  bool rf_wide;        // ... u64
-  u32 rf_par;                          // which of the two this build uses
-  RfP rfp;  // the parameters that do not change from tick to tick
+  u32* xh_dev = nullptr;   // [4][world][SIM_SREQ_HEAD_WORDS] (one of `allocs`)
+  u32* xh_host = nullptr;  // pinned, same shape
+  hipEvent_t xh_ev[4] = {};
+  u64 xh_tick[4] = {~0ull, ~0ull, ~0ull, ~0ull};  // the tick whose heads slot i holds (~0: none / consumed)
+  // SIM_CF_RANDOM_FANOUT: scratch of the per-tick graph build (rf_* kernels)
+  u32* rf_gcur[2] = {};  // bucket fill counters (two: a build zeroes the next one's)
+  void *rf_ovf[2] = {}, *rf_l1 = nullptr;  // overflow lists (two, likewise) and the buckets' regions: u32 entries when a pair id and a target's offset fit, u64 otherwise
+  bool rf_wide = false;  // ... u64
+  u32 rf_par = 0;                      // which of the two this build uses
+  RfP rfp = {};  // the parameters that do not change from tick to tick
   // The graph of tick s is a function of (seed, s): it is built on a stream of its own, TWO ticks ahead — enqueued when tick
   // s - 1 begins, read by tick s + 1 — so that no tick ever waits for a build (one tick ahead, the build ran in the tail of
   // the tick kernel and the next tick waited 25 us for rf_rows).  rf_rcsr[s % 3] / rf_rsrc[s % 3] = the rows of the packets SENT
   // during tick s: while tick t reads buffer (t - 1) % 3 the builds of t and t + 1 may still be writing the other two.
   // rf_q[i] = the tick whose graph buffer i holds or is getting (~0: none), rf_done[i] marks its build.
-  u32* rf_rcsr[3];
-  u32* rf_rsrc[3];
+  u32* rf_rcsr[3] = {};
+  u32* rf_rsrc[3] = {};
   // ... on a shard (SIM_XCHG_PACKED): the graph of tick s is the SENDING side's — rf_rsrc[s % 3] = the shard's own (target, sender,
   // slot) triples sorted, as pair ids; rf_cntb / rf_btot / rf_xoff [s % 3] = count bytes per target of every destination, bucket
   // totals, where every destination's pairs start — needed when tick s has computed (the pack).  The receiving side's rows
   // (rx_rcsr / rx_rsrc) are made at the start of a tick from the slabs the round's exchange delivered.
-  uint8_t* rf_cntb[3];
-  u32* rf_btot[3];
-  u32* rf_xoff[3];
-  u32 rf_C;            // sender chunks of a shard's packed exchange (sim_config.chunks; 1 otherwise)
-  u32 *rx_rcsr, *rx_rsrc;
-  u32 rx_cap;          // entries rx_rsrc holds (f * Nl, 12 sigma and some)
-  RfxL rfx;
-  u32* xflag;          // pinned host memory the rf / rfx kernels write to: a slab, a count byte or rsrc overflowed -> SIM_ERANGE
-  hipStream_t rf_stream;
-  hipEvent_t rf_done[3], rf_go[2];
-  u64 rf_q[3];
-  bool rf_sync, rf_lean;
-  // view entries and ring buckets on demand; ev_hi / q_hi: no node's event / query clock exceeds them (a clock starts at 1, grows
-  // by one per user event / query somebody originates and is otherwise a maximum of clocks seen; a record or a clock that comes
-  // in over the byte boundary raises the bound to its own time + 1) — so no record's Lamport time does
-  LazyPlanes lz_view, lz_ev, lz_q;
-  u64 ev_hi, q_hi;
-  u32* deep_seen;  // pinned: the longest deep list any launch has had (deep_queue_kernel keeps it; sizes that kernel's grid)
+  uint8_t* rf_cntb[3] = {};
+  u32* rf_btot[3] = {};
+  u32* rf_xoff[3] = {};
+  u32 rf_C = 1;        // sender chunks of a shard's packed exchange (sim_config.chunks; 1 otherwise)
+  u32 *rx_rcsr = nullptr, *rx_rsrc = nullptr;
+  u32 rx_cap = 0;      // entries rx_rsrc holds (f * Nl, 12 sigma and some)
+  RfxL rfx = {};
+  u32* xflag = nullptr;  // pinned host memory the rf / rfx kernels write to: a slab, a count byte or rsrc overflowed -> SIM_ERANGE
+  hipStream_t rf_stream = nullptr;
+  hipEvent_t rf_done[3] = {}, rf_go[2] = {};
+  u64 rf_q[3] = {~0ull, ~0ull, ~0ull};
+  bool rf_sync = false, rf_lean = false;
+  // view entries and ring buckets on demand (SP_VIEW, SP_EV, SP_Q); ev_hi / q_hi: no node's event / query clock exceeds them (a clock
+  // starts at 1, grows by one per user event / query somebody originates and is otherwise a maximum of clocks seen; a record or a clock
+  // that comes in over the byte boundary raises the bound to its own time + 1) — so no record's Lamport time does
+  SplitArr sp[SP_N];
+  u64 ev_hi = 1, q_hi = 1;
+  u32* deep_seen = nullptr;  // pinned: the longest deep list any launch has had (deep_queue_kernel keeps it; sizes that kernel's grid)
   struct TrackState* trk = nullptr;  // device-resident trackers (serf_sim_track.inc); null until the first sim_track_add
   struct SeriesState* ser = nullptr;  // device-resident time series (serf_sim_series.inc); null unless one is running
   struct CensusState* cen = nullptr;  // membership census (serf_sim_census.inc); null unless one is running
+  sim_handle() = default;
+  sim_handle(const sim_handle&) = delete;
+  sim_handle& operator=(const sim_handle&) = delete;
+  ~sim_handle();  // (serf_sim_api.inc, behind the observers' hooks)
 };
-// serf_sim_track.inc: the hooks of sim_step_end / sim_destroy (called only when h->trk)
+// serf_sim_track.inc: the hooks of sim_step_end / ~sim_handle (called only when h->trk)
 static int track_step_end(sim_handle* h);
 static void track_destroy(sim_handle* h);
 // serf_sim_series.inc: likewise (called only when h->ser)
@@ -302,11 +333,33 @@ static void lazy_release(LazyPlanes& L) {
   (void)hipMemAddressFree(L.va, L.va_bytes);
   L.va = nullptr; L.maps.clear(); L.phys.clear(); L.mapped = 0;
 }
-static inline u32 lazy_mapped(const LazyPlanes& L, u32 all) { return L.va ? L.mapped : all; }
+static inline u32 split_mapped(const SplitArr& A) { return A.lz.va ? A.lz.mapped : A.planes; }
 // the planes the rings need for clocks up to ev_hi / q_hi (a time t sits in plane t mod B)
 static int rings_need(sim_handle* h) {
-  int rc = lazy_need(h, h->lz_ev, h->d.X + h->ev_hi + 2);  // (rows 0 .. X-1: the overflow rows)
-  return rc ? rc : lazy_need(h, h->lz_q, h->d.X + h->q_hi + 2);
+  int rc = lazy_need(h, h->sp[SP_EV].lz, h->d.X + h->ev_hi + 2);  // (rows 0 .. X-1: the overflow rows)
+  return rc ? rc : lazy_need(h, h->sp[SP_Q].lz, h->d.X + h->q_hi + 2);
+}
+// Everything the handle holds, whatever sim_create, sim_exchange_init or an observer got as far as setting up.  Nothing is given back
+// while a stream may still use it: all three streams first.
+sim_handle::~sim_handle() {
+  (void)hipStreamSynchronize(stream);
+  if (xstream) (void)hipStreamSynchronize(xstream);
+  if (rf_stream) (void)hipStreamSynchronize(rf_stream);
+  if (trk) track_destroy(this);
+  if (ser) series_destroy(this);
+  if (cen) census_destroy(this);
+  if (xcomm) (void)ncclCommDestroy(xcomm);
+  if (xstream) (void)hipStreamDestroy(xstream);
+  if (rf_stream) (void)hipStreamDestroy(rf_stream);
+  for (hipEvent_t e : {xev_go, xev_done, xh_ev[0], xh_ev[1], xh_ev[2], xh_ev[3], rf_done[0], rf_done[1], rf_done[2], rf_go[0], rf_go[1],
+                       sreq_ev[0], sreq_ev[1], sreq_ev[2]})
+    if (e) (void)hipEventDestroy(e);
+  for (auto& pr : prof) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+  for (void* p : {(void*)xh_host, (void*)sreq_host[0], (void*)sreq_host[1], (void*)sreq_host[2], (void*)xflag, (void*)deep_seen})
+    if (p) (void)hipHostFree(p);
+  if (d_pp) (void)hipFree(d_pp);
+  for (void* p : allocs) (void)hipFree(p);
+  for (SplitArr& A : sp) lazy_release(A.lz);
 }
 #define EV_CAP (1u << 20)
 

@@ -403,3 +403,34 @@ def test_suspect_import_without_an_exchange_of_the_librarys(oracle, hiplib):
             s.suspect_import(1, 0, 1)
         assert ei.value.code == _ffi.EINVAL
         s.close()
+
+
+def test_a_create_that_fails_late_and_a_destroy_with_everything_live(oracle, hiplib):
+    # the two ways a handle goes that no other test walks: (a) sim_create refuses a configuration AFTER it has allocated (cfg_check
+    # passes, the 128 local nodes get their arrays, the random fan-out's set-up then refuses more than 64 shards) — whatever it got
+    # goes back; (b) a handle is closed with trackers, a series, a census, timing events and the build stream's work all live.  Then
+    # the device is as usable as before: a plain handle follows the oracle.
+    rf = _ffi.CF_BASELINE_JOINED | _ffi.CF_RANDOM_FANOUT
+    for _ in range(8):
+        with pytest.raises(_ffi.SimError) as ei:
+            _ffi.Sim(hiplib, _ffi.make_config(16384, vshards=128, shard_count=128, shard_rank=0, flags=rf))
+        assert ei.value.code == _ffi.EINVAL
+    live = _ffi.Sim(hiplib, _ffi.make_config(257, fanout=3, view_slots=32, event_ring=16, query_ring=8, probe_interval=2, flags=rf))
+    live.profile(True)
+    live.user_event(5, 0xC0FFEE, 40)
+    live.inject(3, _ffi.OP_CRASH, 9)
+    live.track_rumour(_ffi.K_EVENT, 0xC0FFEE, 1)
+    live.track_member(9, 1 << _ffi.STATUS_FAILED)
+    live.series_start(0, 1, 64)
+    live.census_start(0, 1, 64, 16)
+    live.step(12)
+    live.close()                                      # never read, nothing stopped
+    kw = dict(fanout=3, view_slots=48, event_ring=16, query_ring=8)
+    g, o = both(oracle, hiplib, 384, **kw)
+    ops = sc.schedule(384, 12, rate=0.5, seed=5, max_member_subjects=20)
+    for s in (g, o):
+        sc.apply_schedule(s, ops)
+    for t in range(4):
+        g.step(4)
+        o.step(4)
+        assert g.digest() == o.digest(), f"diverged by tick {4 * (t + 1)}"

@@ -1,6 +1,8 @@
 """Checkpoint / resume (sim_snapshot / sim_restore): the image is canonical, so a run can be stopped in one
 implementation of the ABI and resumed in another — oracle -> oracle on CPU, oracle <-> HIP on the GPU box.
 (Reference analogue: Snapshotter, serf-core/src/snapshot.rs:117-126,228-347, per node; here per simulation.)"""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -99,3 +101,94 @@ def test_huge_lamport_times_and_odd_ring_sizes(oracle, hiplib):
         assert a.digest() == g.digest(), f"diverged after {10 * (t + 1)} ticks"
     sc.assert_same_state(g, a, "huge clocks")
     assert a.dump(_ffi.ARR_ROWS)["event_clock"].max() > 2 ** 34
+
+
+# ---- malformed images: sim_restore refuses them and leaves the handle the fresh one it was ----
+# The image: header, then 16 x (u64 length, payload) in the order oracle/serf_oracle.c documents.
+SECTIONS = ("rows", "queue", "inbox", "view", "ering", "qring", "slot_of", "subject_of", "base", "upmap", "qtab", "qbits",
+            "ops", "alloc_tick", "qfilt", "tags")
+HEADER = 8 + C.sizeof(_ffi.Config) + 8 + 8 + 16    # magic, abi | config | tick | n_slots, n_pending_ops | ops_dropped, slots_recycled
+N_SLOTS_AT = 8 + C.sizeof(_ffi.Config) + 8
+QF_WORDS = 16                                      # SIM_QF_WORDS: {query id, number of ids, tag mask, sealed, ids[12]}
+
+
+def sections(img):
+    """{name: (where its length word is, where its payload is, its length)}"""
+    at, out = HEADER, {}
+    for name in SECTIONS:
+        n = int.from_bytes(img[at:at + 8].tobytes(), "little")
+        out[name] = (at, at + 8, n)
+        at += 8 + n
+    assert at == img.size, "the walk over the sections ends where the image ends"
+    return out
+
+
+def words(img, sec, name):
+    """a section as a copy of its u32 words"""
+    _, at, n = sec[name]
+    return np.frombuffer(img[at:at + n].tobytes(), "<u4").copy()
+
+
+def patched(img, at, data):
+    out = img.copy()
+    out[at:at + len(data)] = np.frombuffer(bytes(data), np.uint8)
+    return out
+
+
+@pytest.fixture(scope="module")
+def source(oracle):
+    """(image at tick 45, its configuration, the digest at tick 45, the digest 20 ticks later): sparse view, SWIM on, part of
+    the schedule still pending"""
+    a, kw = started(oracle, n=384)
+    img = a.snapshot()
+    d0 = a.digest()
+    a.step(20)
+    return img, kw, d0, a.digest()
+
+
+def truncated_and_mislabelled(img):
+    at_len, _, n = sections(img)["view"]
+    return [("cut to 100 bytes", img[:100]), ("cut by its last byte", img[:-1]),
+            ("the view section's length word raised by 32", patched(img, at_len, (n + 32).to_bytes(8, "little")))]
+
+
+def inconsistent(img, n=384):
+    """images of the right shape whose content would index out of bounds on the device"""
+    sec = sections(img)
+    n_slots, n_pending = (int(x) for x in np.frombuffer(img[N_SLOTS_AT:N_SLOTS_AT + 8].tobytes(), "<u4"))
+    assert n_pending > 0, "part of the schedule is still pending"
+    slot_of, subject_of = words(img, sec, "slot_of"), words(img, sec, "subject_of")
+    taken = np.flatnonzero(subject_of != 0xFFFFFFFF)
+    assert taken.size >= 2 and n_slots >= 2, "slots have been handed out"
+    subj = int(np.flatnonzero(slot_of != 0xFFFFFFFF)[0])
+    a, b = int(taken[0]), int(taken[1])
+    swapped = subject_of.copy()
+    swapped[[a, b]] = swapped[[b, a]]
+    return [("a slot_of entry set to n_slots", patched(img, sec["slot_of"][1] + 4 * subj, n_slots.to_bytes(4, "little"))),
+            ("two subject_of entries swapped", patched(img, sec["subject_of"][1], swapped.tobytes())),
+            ("the first pending operation's node set to N", patched(img, sec["ops"][1] + 12, n.to_bytes(4, "little"))),   # OpEnt: u64 tick, u32 op, u32 node, ...
+            ("a tag-class byte set to 255", patched(img, sec["tags"][1] + 7, b"\xff")),
+            ("a query filter's id count set to SIM_QF_IDS + 1", patched(img, sec["qfilt"][1] + 4 * (3 * QF_WORDS + 1), (_ffi.QF_IDS + 1).to_bytes(4, "little")))]
+
+
+def refuses_all_then_restores(lib, source, cases):
+    img, kw, d0, d20 = source
+    fresh = _ffi.Sim(lib, _ffi.make_config(384, **kw))     # ONE handle throughout
+    for what, bad in cases:
+        with pytest.raises(_ffi.SimError) as ei:
+            fresh.restore(bad)
+        assert ei.value.code == _ffi.EINVAL, what
+    fresh.restore(img)
+    assert fresh.tick == 45 and fresh.digest() == d0, "a refused image left something behind"
+    fresh.step(20)
+    assert fresh.digest() == d20
+
+
+def test_oracle_restore_refuses_malformed_images_and_stays_fresh(oracle, source):
+    refuses_all_then_restores(oracle, source, truncated_and_mislabelled(source[0]))
+
+
+@pytest.mark.gpu
+def test_hip_restore_refuses_malformed_images_and_stays_fresh(hiplib, source):
+    img = source[0]
+    refuses_all_then_restores(hiplib, source, truncated_and_mislabelled(img) + inconsistent(img))
