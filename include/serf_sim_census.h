@@ -28,7 +28,8 @@
  *
  * Out of scope: sharded handles (shard_count > 1, SIM_CF_FORCE_SHARDED) — a census needs the sums over ALL observers;
  * every call below returns SIM_ESTATE on such a handle (vshards > 1 on a handle that holds every node is one handle and
- * is supported); subjects without a slot; per-observer output (sim_members is that).
+ * is supported); subjects without a slot; per-observer output (sim_members is that for one observer; the observer roll,
+ * include/serf_sim_roll.h, reduces the same planes per observer).
  */
 #ifndef SERF_SIM_CENSUS_H
 #define SERF_SIM_CENSUS_H

@@ -158,6 +158,31 @@ def census_split(words, max_subjects):
     return hdr, rec
 
 
+# include/serf_sim_roll.h: observer roll (per running node, how far its view lags and whom it accuses; binned and ranked).  The
+# fourth extension: a version of its own, bound only when the loaded library exports it
+ROLL_SYMBOLS = ("roll_start", "roll_count", "roll_read", "roll_stop", "roll_now", "roll_version")
+ROLL_HEADER_WORDS, ROLL_NODE_WORDS, ROLL_TOP_MAX, ROLL_MAX_SAMPLES = 32, 8, 64, 1 << 20
+ROLL_BY_STALE, ROLL_BY_ACCUSED, ROLL_BY_MISSED = 0, 1, 2
+# a node's record and a sample's header as numpy records: the tables of include/serf_sim_roll.h ("id" = node | running << 32,
+# "listed" = listed | rank_by << 32)
+ROLL_NODE_DTYPE = np.dtype([("id", "<u8"), ("stale", "<u8"), ("unknown", "<u8"), ("false_failed", "<u8"), ("suspects", "<u8"),
+                            ("stale_alive", "<u8"), ("lag", "<u8"), ("behind", "<u8")])
+ROLL_HEADER_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("subjects", "<u8"), ("listed", "<u8"), ("current", "<u8"),
+                              ("stale_sum", "<u8"), ("stale_max", "<u8"), ("unknown_sum", "<u8"), ("accusers_failed", "<u8"),
+                              ("false_failed_sum", "<u8"), ("accusers_suspect", "<u8"), ("suspects_sum", "<u8"),
+                              ("holders_stale_alive", "<u8"), ("stale_alive_sum", "<u8"), ("lag_sum", "<u8"), ("lag_max", "<u8"),
+                              ("stale_bins", "<u8", (16,))])
+assert ROLL_NODE_DTYPE.itemsize == 8 * ROLL_NODE_WORDS and ROLL_HEADER_DTYPE.itemsize == 8 * ROLL_HEADER_WORDS
+
+
+def roll_split(words, top_k):
+    """[samples * (32 + 8 * top_k)] words -> (headers[samples], records[samples][top_k])."""
+    a = np.ascontiguousarray(np.asarray(words, np.uint64)).reshape(-1, ROLL_HEADER_WORDS + top_k * ROLL_NODE_WORDS)
+    hdr = np.ascontiguousarray(a[:, :ROLL_HEADER_WORDS]).view(ROLL_HEADER_DTYPE).reshape(-1)
+    rec = np.ascontiguousarray(a[:, ROLL_HEADER_WORDS:]).view(ROLL_NODE_DTYPE).reshape(-1, top_k)
+    return hdr, rec
+
+
 class Tracker(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32), ("min_inc", C.c_uint32),
                 ("ltime", C.c_uint64), ("start_tick", C.c_uint32), ("max_age", C.c_uint32)]
@@ -337,6 +362,20 @@ class SimLib:
                 fn = getattr(self.dll, prefix + name)
                 fn.restype, fn.argtypes = census[name]
                 self.f[name] = fn
+        roll = {
+            "roll_start": (C.c_int, [H, u32, u32, u32, u32, u32]),
+            "roll_count": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
+            "roll_read": (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)]),
+            "roll_stop": (C.c_int, [H]),
+            "roll_now": (C.c_int, [H, u32, u32, vp, vp, vp]),
+            "roll_version": (u32, []),
+        }
+        self.has_roll = all(hasattr(self.dll, prefix + name) for name in ROLL_SYMBOLS)
+        if self.has_roll:
+            for name in ROLL_SYMBOLS:
+                fn = getattr(self.dll, prefix + name)
+                fn.restype, fn.argtypes = roll[name]
+                self.f[name] = fn
 
     def backend_name(self):
         return self.f["backend_name"]().decode()
@@ -368,6 +407,11 @@ class SimLib:
     def census_version(self):
         """SIM_CENSUS_VERSION of include/serf_sim_census.h, or None when the library has no census."""
         return self.f["census_version"]() if self.has_census else None
+
+
+    def roll_version(self):
+        """SIM_ROLL_VERSION of include/serf_sim_roll.h, or None when the library has no roll."""
+        return self.f["roll_version"]() if self.has_roll else None
 
 
 class Sim:
@@ -533,7 +577,7 @@ class Sim:
         self._ck(self.lib.f["convergence_many"](self.h, n, kinds, keys, lts, seen, C.byref(up)), "sim_convergence_many")
         return [int(x) for x in seen[:n]], up.value
 
-    # ---- the extensions: trackers, series, census (include/serf_sim_<group>.h; the oracle has none of them) ----
+    # ---- the extensions: trackers, series, census, roll (include/serf_sim_<group>.h; the oracle has none of them) ----
     def _ext_fn(self, group, name):
         """sim_<group>_<name> of a library that exports the group."""
         if not getattr(self.lib, "has_trackers" if group == "track" else "has_" + group):
@@ -645,6 +689,45 @@ class Sim:
         got = C.c_uint32()
         self._ck(fn(self.h, hdr.ctypes.data, rec.ctypes.data, cap, C.byref(got)), "sim_census_now")
         return hdr[0], rec[:got.value]
+
+    # ---- observer roll (include/serf_sim_roll.h) ----
+    def roll_start(self, first_tick=0, period=1, capacity=1 << 12, top_k=8, rank_by=ROLL_BY_STALE):
+        """Starts a roll: behind every tick t >= first_tick with (t - first_tick) % period == 0, until `capacity` samples
+        are held (a first_tick that has passed means "now"); a sample keeps the header over all observers and the top_k
+        worst of them by `rank_by` (ROLL_BY_STALE / ROLL_BY_ACCUSED / ROLL_BY_MISSED)."""
+        self._ck(self._ext_fn("roll", "start")(self.h, first_tick, period, capacity, top_k, rank_by), "sim_roll_start")
+        self._roll_top = top_k
+
+    def roll_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        return self._sample_count("roll")
+
+    def roll_read(self, first=0, n=None):
+        """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as (headers, records): numpy
+        arrays of ROLL_HEADER_DTYPE [n] and ROLL_NODE_DTYPE [n][top_k] (a sample's records beyond the listed ones are
+        zero); waits for the handle's stream."""
+        fn = self._ext_fn("roll", "read")
+        if n is None:
+            n = max(0, self.roll_count()[0] - first)
+        stride = ROLL_HEADER_WORDS + getattr(self, "_roll_top", 1) * ROLL_NODE_WORDS
+        out = np.zeros(max(1, n) * stride, np.uint64)
+        got = C.c_uint32()
+        self._ck(fn(self.h, first, n, out.ctypes.data, out.size, C.byref(got)), "sim_roll_read")
+        return roll_split(out[:got.value * stride], getattr(self, "_roll_top", 1))
+
+    def roll_stop(self):
+        """Ends the roll and frees its buffers (the samples are gone)."""
+        self._ck(self._ext_fn("roll", "stop")(self.h), "sim_roll_stop")
+
+    def roll_now(self, top_k=8, rank_by=ROLL_BY_STALE, nodes=False):
+        """One roll of the state the handle is in now, with or without a running one: (header, top[top_k]), and with
+        nodes=True (header, top[top_k], every node's record [n_nodes]); waits for the handle's stream."""
+        fn = self._ext_fn("roll", "now")
+        hdr = np.zeros(1, ROLL_HEADER_DTYPE)
+        top = np.zeros(max(1, top_k), ROLL_NODE_DTYPE)
+        every = np.zeros(self.cfg.n_nodes, ROLL_NODE_DTYPE) if nodes else None
+        self._ck(fn(self.h, top_k, rank_by, hdr.ctypes.data, top.ctypes.data, every.ctypes.data if nodes else None), "sim_roll_now")
+        return (hdr[0], top[:top_k], every) if nodes else (hdr[0], top[:top_k])
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

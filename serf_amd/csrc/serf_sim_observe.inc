@@ -1,6 +1,6 @@
 // serf_sim_observe.inc — part of the translation unit serf_sim.hip (included from there, behind the tick kernel; not a header of its own).
 // What the observers of the simulated cluster share on the device — convergence, cluster stats and digests (serf_sim_kernels.inc), trackers,
-// series, census: wave reductions, the fold of a row of per-workgroup partial results, "has node l applied this rumour?".  Their shared
+// series, census, roll: wave reductions, the fold of a row of per-workgroup partial results, "has node l applied this rumour?".  Their shared
 // host part (observer_usable, Sampler) needs the handle: end of serf_sim_host.inc.  Nothing the tick kernel uses is here.
 
 // ---- a value per lane -> the wave's sum / min / max, in every lane ----

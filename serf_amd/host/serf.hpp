@@ -22,6 +22,7 @@
 #include "../../include/serf_sim_track.h"
 #include "../../include/serf_sim_series.h"
 #include "../../include/serf_sim_census.h"
+#include "../../include/serf_sim_roll.h"
 #include "wire.hpp"
 
 namespace serf {
@@ -276,6 +277,49 @@ class Cluster {
     s.subjects.resize(got);
     return s;
   }
+  // observer roll (include/serf_sim_roll.h): behind every period-th tick a header over the running nodes — how many subjects they
+  // do not know or know at an older time than somebody else, how many running members they hold Failed or Suspect, how many
+  // stopped ones Alive, as sums, maxima and a histogram — and the top_k worst of them by `rank_by`.  HIP library only.
+  struct RollSample {
+    sim_roll_header header;
+    std::vector<sim_roll_node> top;    // the listed ones (header.w[3] & 0xFFFFFFFF of them): descending score, ties in ascending id
+    std::vector<sim_roll_node> nodes;  // roll_now(.., true) only: every node's record, in id order
+  };
+  void roll_start(uint32_t first_tick = 0, uint32_t period = 1, uint32_t capacity = 1u << 12, uint32_t top_k = 8,
+                  uint32_t rank_by = SIM_ROLL_BY_STALE) {
+    check(sim_roll_start(h_, first_tick, period, capacity, top_k, rank_by), "sim_roll_start");
+    roll_top_ = top_k;
+  }
+  std::pair<uint32_t, uint32_t> roll_count() const {  // (samples taken, dropped with the buffer full); waits for nothing
+    uint32_t t = 0, d = 0;
+    check(sim_roll_count(h_, &t, &d), "sim_roll_count");
+    return {t, d};
+  }
+  std::vector<RollSample> roll_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    if (n == 0xFFFFFFFFu) { const uint32_t t = roll_count().first; n = t > first ? t - first : 0; }
+    const size_t stride = SIM_ROLL_HEADER_WORDS + (size_t)roll_top_ * SIM_ROLL_NODE_WORDS;
+    std::vector<uint64_t> words((n ? n : 1) * stride);
+    uint32_t got = 0;
+    check(sim_roll_read(h_, first, n, words.data(), words.size(), &got), "sim_roll_read");
+    std::vector<RollSample> out(got);
+    for (uint32_t i = 0; i < got; ++i) {
+      const uint64_t* w = words.data() + i * stride;
+      std::memcpy(&out[i].header, w, sizeof(sim_roll_header));
+      out[i].top.resize((size_t)(out[i].header.w[3] & 0xFFFFFFFFu));
+      if (!out[i].top.empty()) std::memcpy(out[i].top.data(), w + SIM_ROLL_HEADER_WORDS, out[i].top.size() * sizeof(sim_roll_node));
+    }
+    return out;
+  }
+  void roll_stop() { check(sim_roll_stop(h_), "sim_roll_stop"); }
+  // the state the handle is in now, with or without a running roll
+  RollSample roll_now(uint32_t top_k = 8, uint32_t rank_by = SIM_ROLL_BY_STALE, bool nodes = false) {
+    RollSample s;
+    s.top.resize(top_k ? top_k : 1);
+    if (nodes) s.nodes.resize(n_);
+    check(sim_roll_now(h_, top_k, rank_by, &s.header, s.top.data(), nodes ? s.nodes.data() : nullptr), "sim_roll_now");
+    s.top.resize((size_t)(s.header.w[3] & 0xFFFFFFFFu));
+    return s;
+  }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;
@@ -291,6 +335,7 @@ class Cluster {
   sim_handle* h_ = nullptr;
   uint32_t n_;
   uint32_t census_max_ = 1;  // max_subjects of the running census: the stride of its samples
+  uint32_t roll_top_ = 1;    // top_k of the running roll: likewise
 };
 
 inline std::vector<Member> Serf::members() const {

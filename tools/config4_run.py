@@ -31,8 +31,14 @@ Failed / Suspect-or-Dead and by how many, stopped subjects still held Alive, sto
 under "census", one list per field, with the subjects' records of the run's last tick.  Like --series it changes nothing else about
 the run and goes with either kind of run.  The run of profiles/r09_config4_census.json: see profiles/r09_census.md.
 
+`--roll PERIOD`: an OBSERVER ROLL (include/serf_sim_roll.h) of the same run — behind every PERIOD-th tick every running node's view is
+measured against the per-subject references on the device; the headers' curves (observers that are current, the sums and maxima of
+`stale`, `lag` and the three kinds of accusation, the histogram of `stale`) go into the JSON under "roll", one list per field, with
+the 16 worst observers by `stale` of every sample and, for the run's last tick, the 64 worst by accusations.  Like --census it
+changes nothing else about the run, and the two go together.  The run of profiles/r10_config4_roll.json: see profiles/r10_roll.md.
+
 Needs an MI355X.  Writes one JSON (default profiles/r03_config4_churn5_loss1_swim.json; --tracker: profiles/r07_config4_tracker.json;
---series: profiles/r08_config4_series.json; --census: profiles/r09_config4_census.json)."""
+--series: profiles/r08_config4_series.json; --census: profiles/r09_config4_census.json; --roll: profiles/r10_config4_roll.json)."""
 import argparse
 import json
 import os
@@ -58,6 +64,32 @@ def series_json(args, sim):
     for name in rec.dtype.names:
         if name != "reserved":
             out[name] = rec[name].tolist()
+    return out
+
+
+ROLL_TOP = 16
+
+
+def roll_json(args, sim):
+    """The headers of the run's roll, one list per field of _ffi.ROLL_HEADER_DTYPE, the listed observers of every sample and the
+    worst accusers of the state at the end."""
+    from serf_amd import _ffi
+
+    def nodes(rec):
+        return [{"id": int(r["id"]) & 0xFFFFFFFF, **{f: int(r[f]) for f in rec.dtype.names if f != "id"}} for r in rec]
+    taken, dropped = sim.roll_count()
+    hdr, rec = sim.roll_read()
+    out = {"period": args.roll, "samples": int(taken), "dropped": int(dropped), "top_k": ROLL_TOP, "rank_by": "stale",
+           "what": "include/serf_sim_roll.h: state after the tick `tick` - 1; observers = running nodes, subjects = nodes that own a view "
+                   "slot; per observer: unknown / behind = subjects it does not know / knows at an older Lamport time or incarnation "
+                   "than some observer, stale = their sum, false_failed / suspects = RUNNING subjects it holds Failed / Suspect or Dead, "
+                   "stale_alive = STOPPED subjects it holds Alive, lag = the Lamport times it is behind, summed; current = observers "
+                   "with stale 0; stale_bins = observers with stale 0, 1, 2-3, 4-7, ..."}
+    for name in hdr.dtype.names:
+        out[name] = (hdr[name] & 0xFFFFFFFF).tolist() if name == "listed" else hdr[name].tolist()
+    out["worst_by_stale"] = [nodes(r[:int(h["listed"]) & 0xFFFFFFFF]) for h, r in zip(hdr, rec)]
+    h, top = sim.roll_now(_ffi.ROLL_TOP_MAX, _ffi.ROLL_BY_ACCUSED)
+    out["worst_accusers_at_end"] = nodes(top[:int(h["listed"]) & 0xFFFFFFFF])
     return out
 
 
@@ -173,6 +205,7 @@ def run_tracker(args, sim, lib):
     cs = sim.cluster_stats()
     series = series_json(args, sim) if args.series else None
     census = census_json(args, sim) if args.census else None
+    roll = roll_json(args, sim) if args.roll else None
 
     def rounds(name):
         return [r[name] - t for t, r in done_ev if r[name] != NEVER]
@@ -200,7 +233,9 @@ def run_tracker(args, sim, lib):
         out["series"] = series
     if census:
         out["census"] = census
-    json.dump(out, open(args.out, "w"), indent=None if series or census else 1)
+    if roll:
+        out["roll"] = roll
+    json.dump(out, open(args.out, "w"), indent=None if series or census or roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "sim_step_calls", "crashes", "events", "false_positives", "model_bound_drops", "ops_dropped_no_slot", "wall_s")}), "->", args.out)
     print(json.dumps({"rounds_to_99": out["rounds_to"]["99"], "detection": out["detection"]}))
 
@@ -238,10 +273,11 @@ def main():
     ap.add_argument("--fp-sample", type=int, default=64, help="--tracker: never-crashed nodes watched for false suspicions")
     ap.add_argument("--series", type=int, default=0, metavar="PERIOD", help="sample the cluster gauges on the device behind every PERIOD-th tick (include/serf_sim_series.h) and put the series into the JSON")
     ap.add_argument("--census", type=int, default=0, metavar="PERIOD", help="count the views of every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_census.h) and put the agreement curves into the JSON")
+    ap.add_argument("--roll", type=int, default=0, metavar="PERIOD", help="measure every running node's view against the per-subject references on the device behind every PERIOD-th tick (include/serf_sim_roll.h) and put the curves and the worst observers into the JSON")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
+        args.out = os.path.join(ROOT, "profiles", "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
 
     import numpy as np
     from serf_amd import _ffi
@@ -265,6 +301,8 @@ def main():
         sim.series_start(0, args.series, min(_ffi.SERIES_MAX_SAMPLES, 1 << 16))
     if args.census:
         sim.census_start(0, args.census, min(_ffi.CENSUS_MAX_SAMPLES, 1 << 16), 1)   # (the headers' curves: one record a sample is the least)
+    if args.roll:
+        sim.roll_start(0, args.roll, min(_ffi.ROLL_MAX_SAMPLES, 1 << 16), ROLL_TOP, _ffi.ROLL_BY_STALE)
     if args.tracker:
         return run_tracker(args, sim, lib)
     rng = np.random.default_rng(5)
@@ -320,7 +358,7 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census")},
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll")},
         "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
@@ -347,7 +385,9 @@ def main():
         out["series"] = series_json(args, sim)
     if args.census:
         out["census"] = census_json(args, sim)
-    json.dump(out, open(args.out, "w"), indent=None if args.series or args.census else 1)
+    if args.roll:
+        out["roll"] = roll_json(args, sim)
+    json.dump(out, open(args.out, "w"), indent=None if args.series or args.census or args.roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "churn_events", "rounds_to_99", "model_bound_drops", "ops_dropped_no_slot", "failure_detector", "wall_s")}), "->", args.out)
 
 
