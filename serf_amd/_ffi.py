@@ -183,6 +183,65 @@ def roll_split(words, top_k):
     return hdr, rec
 
 
+# include/serf_sim_ledger.h: rumour ledger (per record identity: reach, queued and in-flight copies behind a tick).  The fifth
+# extension: a version of its own, bound only when the loaded library exports it
+LEDGER_SYMBOLS = ("ledger_start", "ledger_count", "ledger_read", "ledger_stop", "ledger_now", "ledger_version")
+LEDGER_HEADER_WORDS, LEDGER_ENTRY_WORDS, LEDGER_MAX, LEDGER_MAX_SAMPLES = 8, 8, 64, 1 << 20
+# a sample's header and one entry's record as numpy records: the tables of include/serf_sim_ledger.h ("id" = key | kind << 32)
+LEDGER_HEADER_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("n", "<u8"), ("queued", "<u8"), ("in_flight", "<u8"),
+                                ("packets", "<u8"), ("transmits", "<u8"), ("reserved", "<u8")])
+LEDGER_ENTRY_DTYPE = np.dtype([("id", "<u8"), ("val", "<u8"), ("reach", "<u8"), ("holders", "<u8"), ("queued", "<u8"),
+                               ("transmits", "<u8"), ("in_flight", "<u8"), ("fresh", "<u8")])
+assert LEDGER_HEADER_DTYPE.itemsize == 8 * LEDGER_HEADER_WORDS and LEDGER_ENTRY_DTYPE.itemsize == 8 * LEDGER_ENTRY_WORDS
+
+
+def ledger_split(words, n):
+    """[samples * (8 + 8 * n)] words -> (headers[samples], records[samples][n])."""
+    a = np.ascontiguousarray(np.asarray(words, np.uint64)).reshape(-1, LEDGER_HEADER_WORDS + n * LEDGER_ENTRY_WORDS)
+    hdr = np.ascontiguousarray(a[:, :LEDGER_HEADER_WORDS]).view(LEDGER_HEADER_DTYPE).reshape(-1)
+    rec = np.ascontiguousarray(a[:, LEDGER_HEADER_WORDS:]).view(LEDGER_ENTRY_DTYPE).reshape(-1, n)
+    return hdr, rec
+
+
+def ledger_summary(headers, records):
+    """What a ledger's samples say about each entry, in the entries' order — a list of dicts:
+      kind, key, val   the identity
+      first_tick       the tick word of the first sample with any reach or carriage (queued + in flight), None when there is none
+      reach, running   of the last sample
+      copies           the sum of in_flight over the samples (with period 1: the copies the cluster sent)
+      died_at          the tick word of the last sample with queued + in_flight > 0 when a later sample exists, else None
+      reach_at_death   the reach at that sample, else None
+      copies_per_node  copies / reach (None while nobody has been reached)
+    headers, records: as Sim.ledger_read returns them."""
+    headers, records = np.asarray(headers), np.asarray(records)
+    out = []
+    for i in range(records.shape[1] if records.ndim == 2 and len(records) else 0):   # (no sample: nothing to say)
+        r = records[:, i]
+        ticks = headers["tick"].astype(np.int64)
+        carried = (r["queued"].astype(np.int64) + r["in_flight"].astype(np.int64)) > 0
+        seen = np.nonzero(carried | (r["reach"] > 0))[0]
+        last = np.nonzero(carried)[0]
+        died = len(last) > 0 and last[-1] + 1 < len(r)
+        reach, copies = int(r["reach"][-1]), int(r["in_flight"].astype(np.int64).sum())
+        out.append(dict(kind=int(r["id"][0] >> np.uint64(32)), key=int(r["id"][0] & np.uint64(0xFFFFFFFF)), val=int(r["val"][0]),
+                        first_tick=int(ticks[seen[0]]) if len(seen) else None,
+                        reach=reach, running=int(headers["running"][-1]), copies=copies,
+                        died_at=int(ticks[last[-1]]) if died else None,
+                        reach_at_death=int(r["reach"][last[-1]]) if died else None,
+                        copies_per_node=copies / reach if reach else None))
+    return out
+
+
+class LedgerEntry(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("key", C.c_uint32), ("val", C.c_uint64)]
+
+
+def ledger_entries(entries):
+    """(kind, key, val) triples (or LedgerEntry) -> a ctypes array of LedgerEntry."""
+    es = [e if isinstance(e, LedgerEntry) else LedgerEntry(int(e[0]), int(e[1]), int(e[2])) for e in entries]
+    return (LedgerEntry * max(1, len(es)))(*es)
+
+
 class Tracker(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32), ("min_inc", C.c_uint32),
                 ("ltime", C.c_uint64), ("start_tick", C.c_uint32), ("max_age", C.c_uint32)]
@@ -376,6 +435,20 @@ class SimLib:
                 fn = getattr(self.dll, prefix + name)
                 fn.restype, fn.argtypes = roll[name]
                 self.f[name] = fn
+        ledger = {
+            "ledger_start": (C.c_int, [H, C.POINTER(LedgerEntry), u32, u32, u32, u32]),
+            "ledger_count": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
+            "ledger_read": (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)]),
+            "ledger_stop": (C.c_int, [H]),
+            "ledger_now": (C.c_int, [H, C.POINTER(LedgerEntry), u32, vp]),
+            "ledger_version": (u32, []),
+        }
+        self.has_ledger = all(hasattr(self.dll, prefix + name) for name in LEDGER_SYMBOLS)
+        if self.has_ledger:
+            for name in LEDGER_SYMBOLS:
+                fn = getattr(self.dll, prefix + name)
+                fn.restype, fn.argtypes = ledger[name]
+                self.f[name] = fn
 
     def backend_name(self):
         return self.f["backend_name"]().decode()
@@ -412,6 +485,10 @@ class SimLib:
     def roll_version(self):
         """SIM_ROLL_VERSION of include/serf_sim_roll.h, or None when the library has no roll."""
         return self.f["roll_version"]() if self.has_roll else None
+
+    def ledger_version(self):
+        """SIM_LEDGER_VERSION of include/serf_sim_ledger.h, or None when the library has no ledger."""
+        return self.f["ledger_version"]() if self.has_ledger else None
 
 
 class Sim:
@@ -577,7 +654,7 @@ class Sim:
         self._ck(self.lib.f["convergence_many"](self.h, n, kinds, keys, lts, seen, C.byref(up)), "sim_convergence_many")
         return [int(x) for x in seen[:n]], up.value
 
-    # ---- the extensions: trackers, series, census, roll (include/serf_sim_<group>.h; the oracle has none of them) ----
+    # ---- the extensions: trackers, series, census, roll, ledger (include/serf_sim_<group>.h; the oracle has none of them) ----
     def _ext_fn(self, group, name):
         """sim_<group>_<name> of a library that exports the group."""
         if not getattr(self.lib, "has_trackers" if group == "track" else "has_" + group):
@@ -728,6 +805,46 @@ class Sim:
         every = np.zeros(self.cfg.n_nodes, ROLL_NODE_DTYPE) if nodes else None
         self._ck(fn(self.h, top_k, rank_by, hdr.ctypes.data, top.ctypes.data, every.ctypes.data if nodes else None), "sim_roll_now")
         return (hdr[0], top[:top_k], every) if nodes else (hdr[0], top[:top_k])
+
+    # ---- rumour ledger (include/serf_sim_ledger.h) ----
+    def ledger_start(self, entries=(), first_tick=0, period=1, capacity=1 << 12):
+        """Starts a ledger of `entries` ((kind, key, val) triples: a record identity each, 64 at most): behind every tick
+        t >= first_tick with (t - first_tick) % period == 0, until `capacity` samples are held (a first_tick that has passed
+        means "now"), a header and per entry its reach, holders, queued copies, their transmits, the copies in flight and
+        the fresh ones."""
+        fn = self._ext_fn("ledger", "start")
+        self._ck(fn(self.h, ledger_entries(entries), len(entries), first_tick, period, capacity), "sim_ledger_start")
+        self._ledger_n = len(entries)
+
+    def ledger_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        return self._sample_count("ledger")
+
+    def ledger_read(self, first=0, n=None):
+        """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as (headers, records): numpy
+        arrays of LEDGER_HEADER_DTYPE [n] and LEDGER_ENTRY_DTYPE [n][entries]; waits for the handle's stream."""
+        fn = self._ext_fn("ledger", "read")
+        if n is None:
+            n = max(0, self.ledger_count()[0] - first)
+        ne = getattr(self, "_ledger_n", 1)
+        stride = LEDGER_HEADER_WORDS + ne * LEDGER_ENTRY_WORDS
+        out = np.zeros(max(1, n) * stride, np.uint64)
+        got = C.c_uint32()
+        self._ck(fn(self.h, first, n, out.ctypes.data, out.size, C.byref(got)), "sim_ledger_read")
+        return ledger_split(out[:got.value * stride], ne)
+
+    def ledger_stop(self):
+        """Ends the ledger and frees its buffers (the samples are gone)."""
+        self._ck(self._ext_fn("ledger", "stop")(self.h), "sim_ledger_stop")
+
+    def ledger_now(self, entries=()):
+        """One ledger sample of the state the handle is in now, with or without a running ledger, for entries of its own:
+        (header, records[len(entries)]); waits for the handle's stream."""
+        fn = self._ext_fn("ledger", "now")
+        out = np.zeros(LEDGER_HEADER_WORDS + max(1, len(entries)) * LEDGER_ENTRY_WORDS, np.uint64)
+        self._ck(fn(self.h, ledger_entries(entries), len(entries), out.ctypes.data), "sim_ledger_now")
+        hdr, rec = ledger_split(out[:LEDGER_HEADER_WORDS + len(entries) * LEDGER_ENTRY_WORDS], len(entries))
+        return hdr[0], rec[0]
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

@@ -82,3 +82,4 @@ extern "C" {
 #include "serf_sim_series.inc"  // include/serf_sim_series.h: likewise
 #include "serf_sim_census.inc"  // include/serf_sim_census.h: likewise
 #include "serf_sim_roll.inc"  // include/serf_sim_roll.h: likewise
+#include "serf_sim_ledger.inc"  // include/serf_sim_ledger.h: likewise

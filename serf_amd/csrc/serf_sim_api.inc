@@ -1201,7 +1201,8 @@ int sim_step_end(sim_handle* h) {
   if (h->trk) { if (int rc = track_step_end(h)) return rc; }  // registered trackers: the tick's evaluation follows it on the stream
   if (h->ser) { if (int rc = series_step_end(h)) return rc; }  // a running series: the tick's sample, when one is due, likewise
   if (h->cen) { if (int rc = census_step_end(h)) return rc; }  // a running census: likewise
-  if (h->rol) return roll_step_end(h);  // a running roll: likewise
+  if (h->rol) { if (int rc = roll_step_end(h)) return rc; }  // a running roll: likewise
+  if (h->led) return ledger_step_end(h);  // a running ledger: likewise
   return SIM_OK;
 }
 // the list of one finished tick out of its buffer (sorted by prober); marks it read

@@ -168,6 +168,7 @@ struct sim_handle {
   struct SeriesState* ser = nullptr;  // device-resident time series (serf_sim_series.inc); null unless one is running
   struct CensusState* cen = nullptr;  // membership census (serf_sim_census.inc); null unless one is running
   struct RollState* rol = nullptr;  // observer roll (serf_sim_roll.inc); null unless one is running
+  struct LedgerState* led = nullptr;  // rumour ledger (serf_sim_ledger.inc); null unless one is running
   sim_handle() = default;
   sim_handle(const sim_handle&) = delete;
   sim_handle& operator=(const sim_handle&) = delete;
@@ -185,6 +186,9 @@ static void census_destroy(sim_handle* h);
 // serf_sim_roll.inc: likewise (called only when h->rol)
 static int roll_step_end(sim_handle* h);
 static void roll_destroy(sim_handle* h);
+// serf_sim_ledger.inc: likewise (called only when h->led)
+static int ledger_step_end(sim_handle* h);
+static void ledger_destroy(sim_handle* h);
 
 #define HCHECK(x)                                                                        \
   do {                                                                                   \
@@ -353,6 +357,7 @@ sim_handle::~sim_handle() {
   if (ser) series_destroy(this);
   if (cen) census_destroy(this);
   if (rol) roll_destroy(this);
+  if (led) ledger_destroy(this);
   if (xcomm) (void)ncclCommDestroy(xcomm);
   if (xstream) (void)hipStreamDestroy(xstream);
   if (rf_stream) (void)hipStreamDestroy(rf_stream);
@@ -369,7 +374,7 @@ sim_handle::~sim_handle() {
 #define EV_CAP (1u << 20)
 
 // ---- what the observers share on the host (the device part: serf_sim_observe.inc; it stands here because it needs the handle) ----
-// trackers, series, census and roll watch a handle that holds every node, between ticks
+// trackers, series, census, roll and ledger watch a handle that holds every node, between ticks
 static int observer_usable(const sim_handle* h) {
   if (!h) return SIM_EINVAL;
   if (h->d.sharded || h->in_tick) return SIM_ESTATE;

@@ -23,6 +23,7 @@
 #include "../../include/serf_sim_series.h"
 #include "../../include/serf_sim_census.h"
 #include "../../include/serf_sim_roll.h"
+#include "../../include/serf_sim_ledger.h"
 #include "wire.hpp"
 
 namespace serf {
@@ -320,6 +321,42 @@ class Cluster {
     s.top.resize((size_t)(s.header.w[3] & 0xFFFFFFFFu));
     return s;
   }
+  // rumour ledger (include/serf_sim_ledger.h): behind every period-th tick, for each of up to 64 record identities (kind, key, val),
+  // how many running nodes have applied the rumour, how many hold it in their queues, the copies queued and their transmits, the
+  // copies in flight and the fresh ones — what a rumour costs and when it dies.  HIP library only.
+  struct LedgerSample {
+    uint64_t header[SIM_LEDGER_HEADER_WORDS];  // tick, running, n, queued, in flight, packets, transmits, 0
+    struct Entry { uint64_t id, val, reach, holders, queued, transmits, in_flight, fresh; };  // id = key | kind << 32
+    std::vector<Entry> entries;                // in the order they were given
+  };
+  void ledger_start(const std::vector<sim_ledger_entry>& e, uint32_t first_tick = 0, uint32_t period = 1, uint32_t capacity = 1u << 12) {
+    check(sim_ledger_start(h_, e.data(), (uint32_t)e.size(), first_tick, period, capacity), "sim_ledger_start");
+    ledger_n_ = (uint32_t)e.size();
+  }
+  std::pair<uint32_t, uint32_t> ledger_count() const {  // (samples taken, dropped with the buffer full); waits for nothing
+    uint32_t t = 0, d = 0;
+    check(sim_ledger_count(h_, &t, &d), "sim_ledger_count");
+    return {t, d};
+  }
+  std::vector<LedgerSample> ledger_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    if (n == 0xFFFFFFFFu) { const uint32_t t = ledger_count().first; n = t > first ? t - first : 0; }
+    const size_t stride = SIM_LEDGER_HEADER_WORDS + (size_t)ledger_n_ * SIM_LEDGER_ENTRY_WORDS;
+    std::vector<uint64_t> words((n ? n : 1) * stride);
+    uint32_t got = 0;
+    check(sim_ledger_read(h_, first, n, words.data(), words.size(), &got), "sim_ledger_read");
+    std::vector<LedgerSample> out(got);
+    for (uint32_t i = 0; i < got; ++i) ledger_unpack(words.data() + i * stride, ledger_n_, out[i]);
+    return out;
+  }
+  void ledger_stop() { check(sim_ledger_stop(h_), "sim_ledger_stop"); }
+  // the state the handle is in now, with or without a running ledger, for entries of its own
+  LedgerSample ledger_now(const std::vector<sim_ledger_entry>& e) {
+    std::vector<uint64_t> words(SIM_LEDGER_HEADER_WORDS + (e.size() ? e.size() : 1) * SIM_LEDGER_ENTRY_WORDS);
+    check(sim_ledger_now(h_, e.data(), (uint32_t)e.size(), words.data()), "sim_ledger_now");
+    LedgerSample s;
+    ledger_unpack(words.data(), (uint32_t)e.size(), s);
+    return s;
+  }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;
@@ -336,6 +373,13 @@ class Cluster {
   uint32_t n_;
   uint32_t census_max_ = 1;  // max_subjects of the running census: the stride of its samples
   uint32_t roll_top_ = 1;    // top_k of the running roll: likewise
+  uint32_t ledger_n_ = 1;    // entries of the running ledger: likewise
+  static void ledger_unpack(const uint64_t* w, uint32_t n, LedgerSample& s) {
+    static_assert(sizeof(LedgerSample::Entry) == 8 * SIM_LEDGER_ENTRY_WORDS, "an entry's record is eight words");
+    std::memcpy(s.header, w, sizeof s.header);
+    s.entries.resize(n);
+    if (n) std::memcpy(s.entries.data(), w + SIM_LEDGER_HEADER_WORDS, (size_t)n * sizeof(LedgerSample::Entry));
+  }
 };
 
 inline std::vector<Member> Serf::members() const {

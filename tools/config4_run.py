@@ -37,6 +37,13 @@ measured against the per-subject references on the device; the headers' curves (
 the 16 worst observers by `stale` of every sample and, for the run's last tick, the 64 worst by accusations.  Like --census it
 changes nothing else about the run, and the two go together.  The run of profiles/r10_config4_roll.json: see profiles/r10_roll.md.
 
+`--ledger PERIOD` (with --tracker): a RUMOUR LEDGER (include/serf_sim_ledger.h) of the first 64 user events the trackers follow —
+behind every PERIOD-th tick their reach, the copies of them that wait in queues and the copies in flight.  A ledger's entries are
+fixed for its life and an event's Lamport time is known only when it is injected, so every burst gets a ledger of its own, started
+with the burst and read, summarised (_ffi.ledger_summary: first tick, final reach, copies sent, the tick it died at and the reach
+then, copies per node reached) and stopped when the next burst comes: a rumour that outlives the stretch between two bursts shows
+"died_at": null.  The summaries go into the JSON under "ledger".  See profiles/r11_ledger.md.
+
 Needs an MI355X.  Writes one JSON (default profiles/r03_config4_churn5_loss1_swim.json; --tracker: profiles/r07_config4_tracker.json;
 --series: profiles/r08_config4_series.json; --census: profiles/r09_config4_census.json; --roll: profiles/r10_config4_roll.json)."""
 import argparse
@@ -91,6 +98,42 @@ def roll_json(args, sim):
     h, top = sim.roll_now(_ffi.ROLL_TOP_MAX, _ffi.ROLL_BY_ACCUSED)
     out["worst_accusers_at_end"] = nodes(top[:int(h["listed"]) & 0xFFFFFFFF])
     return out
+
+
+class LedgerRun:
+    """--ledger: one ledger per burst of user events until LEDGER_MAX rumours have been followed."""
+
+    def __init__(self, args, sim):
+        from serf_amd import _ffi
+        self.ffi, self.args, self.sim = _ffi, args, sim
+        self.followed, self.open_at, self.done, self.dropped = 0, None, [], 0
+
+    def close(self):
+        if self.open_at is None:
+            return
+        self.dropped += self.sim.ledger_count()[1]
+        hdr, rec = self.sim.ledger_read()
+        for s in self.ffi.ledger_summary(hdr, rec):
+            self.done.append({"injected_at": self.open_at, "samples": len(hdr), **s})
+        self.sim.ledger_stop()
+        self.open_at = None
+
+    def burst(self, t, rumours):
+        """rumours: (kind, key, ltime) of the events about to be injected at tick t."""
+        if self.followed >= self.ffi.LEDGER_MAX:
+            return
+        self.close()
+        take = rumours[:self.ffi.LEDGER_MAX - self.followed]
+        self.sim.ledger_start(take, 0, self.args.ledger, 1 << 12)
+        self.open_at, self.followed = int(t), self.followed + len(take)
+
+    def json(self):
+        self.close()
+        return {"period": self.args.ledger, "rumours": self.done, "dropped": self.dropped,
+                "what": "include/serf_sim_ledger.h: per followed user event (the first 64, a ledger per burst, ended by the next burst): "
+                        "first_tick = sim_tick of the first sample with any reach or carriage; reach / running = at the ledger's last "
+                        "sample; copies = the sum of the in-flight column (period 1: the copies the cluster sent); died_at = sim_tick "
+                        "of the last sample with a copy queued or in flight when a later sample exists; copies_per_node = copies / reach"}
 
 
 def census_json(args, sim):
@@ -151,6 +194,7 @@ def run_tracker(args, sim, lib):
     every = max(1, (total - 100) // bursts)
     live_ev, done_ev, done_cr = [], [], []   # (id, inject tick) / (inject tick, result) / (crash tick, suspect+, failed)
     ci = 0
+    ledger = LedgerRun(args, sim) if args.ledger else None
     t0 = time.perf_counter()
     stretches = 0
 
@@ -194,6 +238,8 @@ def run_tracker(args, sim, lib):
                 specs.append(_ffi.rumour_tracker(_ffi.K_EVENT, key, sim.stats(node).event_time, max_age=args.max_rounds))
                 keys.append((node, key))
             live_ev += [(i, t) for i in sim.track_add(specs)]
+            if ledger:
+                ledger.burst(t, [(sp.a, sp.b, sp.ltime) for sp in specs])
             for node, key in keys:
                 sim.user_event(node, key, 64)
         sim.step(min(every, total - t))     # ONE call per stretch; nothing is read back inside it
@@ -206,6 +252,7 @@ def run_tracker(args, sim, lib):
     series = series_json(args, sim) if args.series else None
     census = census_json(args, sim) if args.census else None
     roll = roll_json(args, sim) if args.roll else None
+    ledger = ledger.json() if ledger else None
 
     def rounds(name):
         return [r[name] - t for t, r in done_ev if r[name] != NEVER]
@@ -235,6 +282,8 @@ def run_tracker(args, sim, lib):
         out["census"] = census
     if roll:
         out["roll"] = roll
+    if ledger:
+        out["ledger"] = ledger
     json.dump(out, open(args.out, "w"), indent=None if series or census or roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "sim_step_calls", "crashes", "events", "false_positives", "model_bound_drops", "ops_dropped_no_slot", "wall_s")}), "->", args.out)
     print(json.dumps({"rounds_to_99": out["rounds_to"]["99"], "detection": out["detection"]}))
@@ -274,10 +323,13 @@ def main():
     ap.add_argument("--series", type=int, default=0, metavar="PERIOD", help="sample the cluster gauges on the device behind every PERIOD-th tick (include/serf_sim_series.h) and put the series into the JSON")
     ap.add_argument("--census", type=int, default=0, metavar="PERIOD", help="count the views of every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_census.h) and put the agreement curves into the JSON")
     ap.add_argument("--roll", type=int, default=0, metavar="PERIOD", help="measure every running node's view against the per-subject references on the device behind every PERIOD-th tick (include/serf_sim_roll.h) and put the curves and the worst observers into the JSON")
+    ap.add_argument("--ledger", type=int, default=0, metavar="PERIOD", help="--tracker: follow the first 64 user events with rumour ledgers, sampled behind every PERIOD-th tick (include/serf_sim_ledger.h), and put their summaries into the JSON")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.ledger and not args.tracker:
+        ap.error("--ledger follows the rumours of a --tracker run")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
+        args.out = os.path.join(ROOT, "profiles", "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
 
     import numpy as np
     from serf_amd import _ffi
@@ -358,7 +410,7 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll")},
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger")},
         "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
