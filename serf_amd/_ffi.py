@@ -150,12 +150,18 @@ CENSUS_HEADER_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("subjects"
 assert CENSUS_SUBJECT_DTYPE.itemsize == CENSUS_HEADER_DTYPE.itemsize == 8 * CENSUS_WORDS
 
 
+def sample_split(words, hdr_dtype, rec_dtype, per_sample):
+    """[samples * (a header + per_sample records)] words -> (headers[samples], records[samples][per_sample])."""
+    hw, rw = hdr_dtype.itemsize // 8, rec_dtype.itemsize // 8
+    a = np.ascontiguousarray(np.asarray(words, np.uint64)).reshape(-1, hw + per_sample * rw)
+    hdr = np.ascontiguousarray(a[:, :hw]).view(hdr_dtype).reshape(-1)
+    rec = np.ascontiguousarray(a[:, hw:]).view(rec_dtype).reshape(-1, per_sample)
+    return hdr, rec
+
+
 def census_split(words, max_subjects):
     """[samples * (1 + max_subjects) * 16] words -> (headers[samples], records[samples][max_subjects])."""
-    a = np.ascontiguousarray(np.asarray(words, np.uint64)).reshape(-1, 1 + max_subjects, CENSUS_WORDS)
-    hdr = np.ascontiguousarray(a[:, 0, :]).view(CENSUS_HEADER_DTYPE).reshape(-1)
-    rec = np.ascontiguousarray(a[:, 1:, :]).view(CENSUS_SUBJECT_DTYPE).reshape(-1, max_subjects)
-    return hdr, rec
+    return sample_split(words, CENSUS_HEADER_DTYPE, CENSUS_SUBJECT_DTYPE, max_subjects)
 
 
 # include/serf_sim_roll.h: observer roll (per running node, how far its view lags and whom it accuses; binned and ranked).  The
@@ -177,10 +183,7 @@ assert ROLL_NODE_DTYPE.itemsize == 8 * ROLL_NODE_WORDS and ROLL_HEADER_DTYPE.ite
 
 def roll_split(words, top_k):
     """[samples * (32 + 8 * top_k)] words -> (headers[samples], records[samples][top_k])."""
-    a = np.ascontiguousarray(np.asarray(words, np.uint64)).reshape(-1, ROLL_HEADER_WORDS + top_k * ROLL_NODE_WORDS)
-    hdr = np.ascontiguousarray(a[:, :ROLL_HEADER_WORDS]).view(ROLL_HEADER_DTYPE).reshape(-1)
-    rec = np.ascontiguousarray(a[:, ROLL_HEADER_WORDS:]).view(ROLL_NODE_DTYPE).reshape(-1, top_k)
-    return hdr, rec
+    return sample_split(words, ROLL_HEADER_DTYPE, ROLL_NODE_DTYPE, top_k)
 
 
 # include/serf_sim_ledger.h: rumour ledger (per record identity: reach, queued and in-flight copies behind a tick).  The fifth
@@ -197,10 +200,7 @@ assert LEDGER_HEADER_DTYPE.itemsize == 8 * LEDGER_HEADER_WORDS and LEDGER_ENTRY_
 
 def ledger_split(words, n):
     """[samples * (8 + 8 * n)] words -> (headers[samples], records[samples][n])."""
-    a = np.ascontiguousarray(np.asarray(words, np.uint64)).reshape(-1, LEDGER_HEADER_WORDS + n * LEDGER_ENTRY_WORDS)
-    hdr = np.ascontiguousarray(a[:, :LEDGER_HEADER_WORDS]).view(LEDGER_HEADER_DTYPE).reshape(-1)
-    rec = np.ascontiguousarray(a[:, LEDGER_HEADER_WORDS:]).view(LEDGER_ENTRY_DTYPE).reshape(-1, n)
-    return hdr, rec
+    return sample_split(words, LEDGER_HEADER_DTYPE, LEDGER_ENTRY_DTYPE, n)
 
 
 def ledger_summary(headers, records):
@@ -381,73 +381,59 @@ class SimLib:
             fn = getattr(self.dll, prefix + name)  # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             self.f[name] = fn
-        track = {
-            "track_add": (C.c_int, [H, C.POINTER(Tracker), u32, C.POINTER(u32)]),
-            "track_remove": (C.c_int, [H, C.POINTER(u32), u32]),
-            "track_read": (C.c_int, [H, C.POINTER(u32), u32, C.POINTER(TrackResult)]),
-            "track_active": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
-            "track_version": (u32, []),
-        }
-        self.has_trackers = all(hasattr(self.dll, prefix + name) for name in TRACK_SYMBOLS)
-        if self.has_trackers:
-            for name in TRACK_SYMBOLS:
+        # the five extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
+        # bound whole or not at all
+        count = (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)])
+        read = (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)])
+        stop = (C.c_int, [H])
+        ext = [
+            ("track", "has_trackers", {
+                "track_add": (C.c_int, [H, C.POINTER(Tracker), u32, C.POINTER(u32)]),
+                "track_remove": (C.c_int, [H, C.POINTER(u32), u32]),
+                "track_read": (C.c_int, [H, C.POINTER(u32), u32, C.POINTER(TrackResult)]),
+                "track_active": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
+                "track_version": (u32, []),
+            }),
+            ("series", "has_series", {
+                "series_start": (C.c_int, [H, u32, u32, u32]),
+                "series_count": count,
+                "series_read": (C.c_int, [H, u32, u32, vp, C.POINTER(u32)]),
+                "series_stop": stop,
+                "series_version": (u32, []),
+            }),
+            ("census", "has_census", {
+                "census_start": (C.c_int, [H, u32, u32, u32, u32]),
+                "census_count": count,
+                "census_read": read,
+                "census_stop": stop,
+                "census_now": (C.c_int, [H, vp, vp, u32, C.POINTER(u32)]),
+                "census_version": (u32, []),
+            }),
+            ("roll", "has_roll", {
+                "roll_start": (C.c_int, [H, u32, u32, u32, u32, u32]),
+                "roll_count": count,
+                "roll_read": read,
+                "roll_stop": stop,
+                "roll_now": (C.c_int, [H, u32, u32, vp, vp, vp]),
+                "roll_version": (u32, []),
+            }),
+            ("ledger", "has_ledger", {
+                "ledger_start": (C.c_int, [H, C.POINTER(LedgerEntry), u32, u32, u32, u32]),
+                "ledger_count": count,
+                "ledger_read": read,
+                "ledger_stop": stop,
+                "ledger_now": (C.c_int, [H, C.POINTER(LedgerEntry), u32, vp]),
+                "ledger_version": (u32, []),
+            }),
+        ]
+        assert [tuple(sigs) for _, _, sigs in ext] == [TRACK_SYMBOLS, SERIES_SYMBOLS, CENSUS_SYMBOLS, ROLL_SYMBOLS, LEDGER_SYMBOLS]
+        self.ext = {}   # group -> exported
+        for group, attr, sigs in ext:
+            self.ext[group] = all(hasattr(self.dll, prefix + name) for name in sigs)
+            setattr(self, attr, self.ext[group])
+            for name, (res, args) in sigs.items() if self.ext[group] else ():
                 fn = getattr(self.dll, prefix + name)
-                fn.restype, fn.argtypes = track[name]
-                self.f[name] = fn
-        series = {
-            "series_start": (C.c_int, [H, u32, u32, u32]),
-            "series_count": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
-            "series_read": (C.c_int, [H, u32, u32, vp, C.POINTER(u32)]),
-            "series_stop": (C.c_int, [H]),
-            "series_version": (u32, []),
-        }
-        self.has_series = all(hasattr(self.dll, prefix + name) for name in SERIES_SYMBOLS)
-        if self.has_series:
-            for name in SERIES_SYMBOLS:
-                fn = getattr(self.dll, prefix + name)
-                fn.restype, fn.argtypes = series[name]
-                self.f[name] = fn
-        census = {
-            "census_start": (C.c_int, [H, u32, u32, u32, u32]),
-            "census_count": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
-            "census_read": (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)]),
-            "census_stop": (C.c_int, [H]),
-            "census_now": (C.c_int, [H, vp, vp, u32, C.POINTER(u32)]),
-            "census_version": (u32, []),
-        }
-        self.has_census = all(hasattr(self.dll, prefix + name) for name in CENSUS_SYMBOLS)
-        if self.has_census:
-            for name in CENSUS_SYMBOLS:
-                fn = getattr(self.dll, prefix + name)
-                fn.restype, fn.argtypes = census[name]
-                self.f[name] = fn
-        roll = {
-            "roll_start": (C.c_int, [H, u32, u32, u32, u32, u32]),
-            "roll_count": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
-            "roll_read": (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)]),
-            "roll_stop": (C.c_int, [H]),
-            "roll_now": (C.c_int, [H, u32, u32, vp, vp, vp]),
-            "roll_version": (u32, []),
-        }
-        self.has_roll = all(hasattr(self.dll, prefix + name) for name in ROLL_SYMBOLS)
-        if self.has_roll:
-            for name in ROLL_SYMBOLS:
-                fn = getattr(self.dll, prefix + name)
-                fn.restype, fn.argtypes = roll[name]
-                self.f[name] = fn
-        ledger = {
-            "ledger_start": (C.c_int, [H, C.POINTER(LedgerEntry), u32, u32, u32, u32]),
-            "ledger_count": (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)]),
-            "ledger_read": (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)]),
-            "ledger_stop": (C.c_int, [H]),
-            "ledger_now": (C.c_int, [H, C.POINTER(LedgerEntry), u32, vp]),
-            "ledger_version": (u32, []),
-        }
-        self.has_ledger = all(hasattr(self.dll, prefix + name) for name in LEDGER_SYMBOLS)
-        if self.has_ledger:
-            for name in LEDGER_SYMBOLS:
-                fn = getattr(self.dll, prefix + name)
-                fn.restype, fn.argtypes = ledger[name]
+                fn.restype, fn.argtypes = res, args
                 self.f[name] = fn
 
     def backend_name(self):
@@ -480,7 +466,6 @@ class SimLib:
     def census_version(self):
         """SIM_CENSUS_VERSION of include/serf_sim_census.h, or None when the library has no census."""
         return self.f["census_version"]() if self.has_census else None
-
 
     def roll_version(self):
         """SIM_ROLL_VERSION of include/serf_sim_roll.h, or None when the library has no roll."""
@@ -657,7 +642,7 @@ class Sim:
     # ---- the extensions: trackers, series, census, roll, ledger (include/serf_sim_<group>.h; the oracle has none of them) ----
     def _ext_fn(self, group, name):
         """sim_<group>_<name> of a library that exports the group."""
-        if not getattr(self.lib, "has_trackers" if group == "track" else "has_" + group):
+        if not self.lib.ext[group]:
             raise NotImplementedError(f"{self.lib.path} exports no sim_{group}_* (include/serf_sim_{group}.h)")
         return self.lib.f[f"{group}_{name}"]
 
@@ -665,6 +650,23 @@ class Sim:
         t, d = C.c_uint32(), C.c_uint32()
         self._ck(self._ext_fn(group, "count")(self.h, C.byref(t), C.byref(d)), f"sim_{group}_count")
         return t.value, d.value
+
+    def _sample_read(self, group, first, n, hdr_dtype, rec_dtype=None, per_sample=0):
+        """sim_<group>_read of samples first .. first + n - 1 (n = None: all that were taken from `first` on), each a header and
+        per_sample records — the running observer's parameter — split into (headers, records); without rec_dtype a sample is
+        one struct (the series) and sim_<group>_read takes no size."""
+        fn = self._ext_fn(group, "read")
+        if n is None:
+            n = max(0, self._sample_count(group)[0] - first)
+        stride = (hdr_dtype.itemsize + per_sample * rec_dtype.itemsize if rec_dtype else hdr_dtype.itemsize) // 8
+        out = np.zeros(max(1, n) * stride, np.uint64)
+        got = C.c_uint32()
+        self._ck(fn(self.h, first, n, out.ctypes.data, *([out.size] if rec_dtype else []), C.byref(got)), f"sim_{group}_read")
+        words = out[:got.value * stride]
+        return sample_split(words, hdr_dtype, rec_dtype, per_sample) if rec_dtype else words.view(hdr_dtype)
+
+    def _sample_stop(self, group):
+        self._ck(self._ext_fn(group, "stop")(self.h), f"sim_{group}_stop")
 
     # ---- device-resident trackers (include/serf_sim_track.h) ----
 
@@ -717,16 +719,11 @@ class Sim:
     def series_read(self, first=0, n=None):
         """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as a numpy array of SERIES_DTYPE;
         waits for the handle's stream."""
-        if n is None:
-            n = max(0, self.series_count()[0] - first)
-        out = np.zeros(max(1, n), SERIES_DTYPE)
-        got = C.c_uint32()
-        self._ck(self._ext_fn("series", "read")(self.h, first, n, out.ctypes.data, C.byref(got)), "sim_series_read")
-        return out[:got.value]
+        return self._sample_read("series", first, n, SERIES_DTYPE)
 
     def series_stop(self):
         """Ends the series and frees its buffers (the samples are gone)."""
-        self._ck(self._ext_fn("series", "stop")(self.h), "sim_series_stop")
+        self._sample_stop("series")
 
     # ---- membership census (include/serf_sim_census.h) ----
     def census_start(self, first_tick=0, period=1, capacity=1 << 12, max_subjects=64):
@@ -744,18 +741,11 @@ class Sim:
         """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as (headers, records): numpy
         arrays of CENSUS_HEADER_DTYPE [n] and CENSUS_SUBJECT_DTYPE [n][max_subjects] (a sample's records beyond
         headers["stored"] are zero); waits for the handle's stream."""
-        fn = self._ext_fn("census", "read")
-        if n is None:
-            n = max(0, self.census_count()[0] - first)
-        ms = getattr(self, "_census_max", 1)
-        out = np.zeros(max(1, n) * (1 + ms) * CENSUS_WORDS, np.uint64)
-        got = C.c_uint32()
-        self._ck(fn(self.h, first, n, out.ctypes.data, out.size, C.byref(got)), "sim_census_read")
-        return census_split(out[:got.value * (1 + ms) * CENSUS_WORDS], ms)
+        return self._sample_read("census", first, n, CENSUS_HEADER_DTYPE, CENSUS_SUBJECT_DTYPE, getattr(self, "_census_max", 1))
 
     def census_stop(self):
         """Ends the census and frees its buffers (the samples are gone)."""
-        self._ck(self._ext_fn("census", "stop")(self.h), "sim_census_stop")
+        self._sample_stop("census")
 
     def census_now(self, cap=64):
         """One census of the state the handle is in now, with or without a running one: (header, records[min(subjects,
@@ -783,18 +773,11 @@ class Sim:
         """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as (headers, records): numpy
         arrays of ROLL_HEADER_DTYPE [n] and ROLL_NODE_DTYPE [n][top_k] (a sample's records beyond the listed ones are
         zero); waits for the handle's stream."""
-        fn = self._ext_fn("roll", "read")
-        if n is None:
-            n = max(0, self.roll_count()[0] - first)
-        stride = ROLL_HEADER_WORDS + getattr(self, "_roll_top", 1) * ROLL_NODE_WORDS
-        out = np.zeros(max(1, n) * stride, np.uint64)
-        got = C.c_uint32()
-        self._ck(fn(self.h, first, n, out.ctypes.data, out.size, C.byref(got)), "sim_roll_read")
-        return roll_split(out[:got.value * stride], getattr(self, "_roll_top", 1))
+        return self._sample_read("roll", first, n, ROLL_HEADER_DTYPE, ROLL_NODE_DTYPE, getattr(self, "_roll_top", 1))
 
     def roll_stop(self):
         """Ends the roll and frees its buffers (the samples are gone)."""
-        self._ck(self._ext_fn("roll", "stop")(self.h), "sim_roll_stop")
+        self._sample_stop("roll")
 
     def roll_now(self, top_k=8, rank_by=ROLL_BY_STALE, nodes=False):
         """One roll of the state the handle is in now, with or without a running one: (header, top[top_k]), and with
@@ -823,19 +806,11 @@ class Sim:
     def ledger_read(self, first=0, n=None):
         """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as (headers, records): numpy
         arrays of LEDGER_HEADER_DTYPE [n] and LEDGER_ENTRY_DTYPE [n][entries]; waits for the handle's stream."""
-        fn = self._ext_fn("ledger", "read")
-        if n is None:
-            n = max(0, self.ledger_count()[0] - first)
-        ne = getattr(self, "_ledger_n", 1)
-        stride = LEDGER_HEADER_WORDS + ne * LEDGER_ENTRY_WORDS
-        out = np.zeros(max(1, n) * stride, np.uint64)
-        got = C.c_uint32()
-        self._ck(fn(self.h, first, n, out.ctypes.data, out.size, C.byref(got)), "sim_ledger_read")
-        return ledger_split(out[:got.value * stride], ne)
+        return self._sample_read("ledger", first, n, LEDGER_HEADER_DTYPE, LEDGER_ENTRY_DTYPE, getattr(self, "_ledger_n", 1))
 
     def ledger_stop(self):
         """Ends the ledger and frees its buffers (the samples are gone)."""
-        self._ck(self._ext_fn("ledger", "stop")(self.h), "sim_ledger_stop")
+        self._sample_stop("ledger")
 
     def ledger_now(self, entries=()):
         """One ledger sample of the state the handle is in now, with or without a running ledger, for entries of its own:

@@ -1199,11 +1199,7 @@ int sim_step_end(sim_handle* h) {
     h->sreq_tick[t % 3] = t;
   }
   if (h->trk) { if (int rc = track_step_end(h)) return rc; }  // registered trackers: the tick's evaluation follows it on the stream
-  if (h->ser) { if (int rc = series_step_end(h)) return rc; }  // a running series: the tick's sample, when one is due, likewise
-  if (h->cen) { if (int rc = census_step_end(h)) return rc; }  // a running census: likewise
-  if (h->rol) { if (int rc = roll_step_end(h)) return rc; }  // a running roll: likewise
-  if (h->led) return ledger_step_end(h);  // a running ledger: likewise
-  return SIM_OK;
+  return observers_step_end(h);  // running series, census, roll, ledger: the tick's sample, when one is due, likewise
 }
 // the list of one finished tick out of its buffer (sorted by prober); marks it read
 static int sreq_take(sim_handle* h, u64 t, uint32_t* out, uint32_t cap_pairs, uint32_t* n_pairs) {

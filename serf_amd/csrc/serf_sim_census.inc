@@ -15,7 +15,7 @@
 //   census_pack_kernel   workgroup 0 walks the slots in ascending order, compacts the allocated ones into the sample (the first
 //                        max_subjects of them) and computes the header over ALL of them; the other workgroups zero the records that stay unused
 // Their order is the stream's.  The host knows every sampled tick in advance: it passes the sample's place to the launches and reads nothing back.
-// A handle without a started census never gets here (sim_step_end tests one pointer).
+// A handle without a started census never gets here (sim_step_end finds its entry of the observers' table null).
 //
 // The segment.  CEN_SEG = 8192 nodes = 128 KiB of heads per workgroup of 256 lanes: 32 loads a lane, issued in batches of CEN_BATCH = 8
 // independent ones (128 bytes a lane, 32 KiB a workgroup in flight — with 8 workgroups a CU about what the latency-bandwidth product of
@@ -252,12 +252,6 @@ __global__ __launch_bounds__(BLOCK) void census_pack_kernel(CenDevP p) {
 }
 
 // ---- host ----
-struct CensusState {
-  DevScratch<u64> d_part;  // [A][SIM_CENSUS_WORDS][S]
-  DevScratch<u64> d_rec;   // [A][SIM_CENSUS_WORDS]
-  Sampler smp;            // samples of (1 + maxsub) * SIM_CENSUS_WORDS words
-  u32 maxsub = 0;
-};
 static inline u32 census_segments(const sim_handle* h) { return (h->d.Nl + CEN_SEG - 1u) / CEN_SEG; }
 static inline size_t census_stride(u32 maxsub) { return ((size_t)maxsub + 1u) * SIM_CENSUS_WORDS; }  // words of a sample
 
@@ -268,15 +262,8 @@ static int census_scratch(const sim_handle* h, DevScratch<u64>& part, DevScratch
   if (int rc = part.alloc((size_t)cells * SIM_CENSUS_WORDS)) return rc;
   return rec.alloc((size_t)h->d.A * SIM_CENSUS_WORDS);
 }
-static void census_destroy(sim_handle* h) {
-  CensusState* s = h->cen;
-  if (!s) return;
-  sampler_close(s->smp);
-  delete s;
-  h->cen = nullptr;
-}
-// one census of the state the stream will be in when it gets here, into out[(1 + maxsub) * SIM_CENSUS_WORDS]
-static int census_launch(sim_handle* h, u64* part, u64* rec, u64* out, u32 maxsub) {
+// the record of every allocated slot into rec (the count and fold kernels; the roll runs them too); returns the parameters they got
+static CenDevP census_records(sim_handle* h, u64* part, u64* rec, u64* out, u32 maxsub) {
   CenDevP p;
   p.view = h->d.view; p.subject_of = h->d.subject_of; p.upmap = h->d.upmap;
   p.N = h->d.N; p.Nl = h->d.Nl;
@@ -289,77 +276,53 @@ static int census_launch(sim_handle* h, u64* part, u64* rec, u64* out, u32 maxsu
     census_count_kernel<<<p.bound * p.S, BLOCK, 0, h->stream>>>(p);
     census_fold_kernel<<<(p.bound + BLOCK / 64 - 1) / (BLOCK / 64), BLOCK, 0, h->stream>>>(p);
   }
+  return p;
+}
+// one census of the state the stream will be in when it gets here, into out[(1 + maxsub) * SIM_CENSUS_WORDS]
+static int census_launch(sim_handle* h, u64* part, u64* rec, u64* out, u32 maxsub) {
+  const CenDevP p = census_records(h, part, rec, out, maxsub);
   census_pack_kernel<<<1u + (maxsub + CEN_ZREC - 1u) / CEN_ZREC, BLOCK, 0, h->stream>>>(p);
   HCHECK(hipGetLastError());
   return SIM_OK;
 }
-// sim_step_end: tick h->tick - 1 has been enqueued; a sample of it follows it on the stream
-static int census_step_end(sim_handle* h) {
-  CensusState* s = h->cen;
-  u64* slot = sampler_slot(h, s->smp);
-  if (!slot) return SIM_OK;
-  if (int rc = census_launch(h, s->d_part.get(), s->d_rec.get(), slot, s->maxsub)) return rc;
-  sampler_commit(s->smp);
-  return SIM_OK;
-}
+struct CensusState : Observer {  // samples of (1 + maxsub) * SIM_CENSUS_WORDS words
+  DevScratch<u64> d_part;  // [A][SIM_CENSUS_WORDS][S]
+  DevScratch<u64> d_rec;   // [A][SIM_CENSUS_WORDS]
+  u32 maxsub = 0;
+  int sample(sim_handle* h, u64* out) override { return census_launch(h, d_part.get(), d_rec.get(), out, maxsub); }
+};
 
 extern "C" {
 
 uint32_t sim_census_version(void) { return SIM_CENSUS_VERSION; }
 
 int sim_census_start(sim_handle* h, uint32_t first_tick, uint32_t period, uint32_t capacity, uint32_t max_subjects) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!period || !capacity || capacity > SIM_CENSUS_MAX_SAMPLES || !max_subjects) return SIM_EINVAL;
-  if (h->cen) return SIM_ESTATE;
   CensusState* s = new CensusState();
-  h->cen = s;
   s->maxsub = max_subjects;
-  if (census_scratch(h, s->d_part, s->d_rec) != SIM_OK ||
-      sampler_open(h, s->smp, first_tick, period, capacity, census_stride(max_subjects)) != SIM_OK) {
-    (void)hipGetLastError();
-    census_destroy(h);
-    return SIM_ENOMEM;
-  }
-  return SIM_OK;
+  return observer_start(h, OB_CENSUS, s, SIM_CENSUS_MAX_SAMPLES, first_tick, period, capacity, census_stride(max_subjects),
+                        [&] { return max_subjects ? SIM_OK : SIM_EINVAL; }, [&] { return census_scratch(h, s->d_part, s->d_rec); });
 }
 
-int sim_census_count(const sim_handle* h, uint32_t* taken, uint32_t* dropped) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!taken || !dropped) return SIM_EINVAL;
-  sampler_count(h->cen ? &h->cen->smp : nullptr, taken, dropped);
-  return SIM_OK;
-}
+int sim_census_count(const sim_handle* h, uint32_t* taken, uint32_t* dropped) { return observer_count(h, OB_CENSUS, taken, dropped); }
 
 int sim_census_read(sim_handle* h, uint32_t first, uint32_t n, uint64_t* out, size_t cap_words, uint32_t* n_out) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!out || !n_out) return SIM_EINVAL;
-  if (!h->cen) return SIM_ESTATE;
-  return sampler_read(h, h->cen->smp, first, n, out, cap_words, n_out);
+  return observer_read(h, OB_CENSUS, first, n, out, cap_words, n_out);
 }
 
-int sim_census_stop(sim_handle* h) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!h->cen) return SIM_ESTATE;
-  HCHECK(hipStreamSynchronize(h->stream));  // (samples still enqueued write into the buffers)
-  census_destroy(h);
-  return SIM_OK;
-}
+int sim_census_stop(sim_handle* h) { return observer_stop(h, OB_CENSUS); }
 
 int sim_census_now(sim_handle* h, sim_census_header* hdr, sim_census_subject* recs, uint32_t cap, uint32_t* n) {
   if (int rc = observer_usable(h)) return rc;
   if (!hdr || !n || (cap && !recs)) return SIM_EINVAL;
   const u32 maxsub = std::min(cap, h->d.A);  // (there are no more subjects than slots)
-  DevScratch<u64> own_part, own_rec, out;
+  DevScratch<u64> own_part, own_rec;
   // (a running census lends its scratch: the stream orders the two uses)
-  if (!h->cen) { if (int rc = census_scratch(h, own_part, own_rec)) return rc; }
-  u64* part = h->cen ? h->cen->d_part.get() : own_part.get();
-  u64* rec = h->cen ? h->cen->d_rec.get() : own_rec.get();
+  CensusState* run = static_cast<CensusState*>(h->obs[OB_CENSUS]);
+  if (!run) { if (int rc = census_scratch(h, own_part, own_rec)) return rc; }
+  u64* part = run ? run->d_part.get() : own_part.get();
+  u64* rec = run ? run->d_rec.get() : own_rec.get();
   std::vector<u64> host(census_stride(maxsub));
-  int rc = out.alloc(host.size());
-  if (rc == SIM_OK) rc = census_launch(h, part, rec, out.get(), maxsub);
-  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == SIM_OK) rc = SIM_EDEVICE;  // (also before the scratch goes)
-  if (rc != SIM_OK) return rc;
-  HCHECK(hipMemcpy(host.data(), out.get(), host.size() * 8, hipMemcpyDeviceToHost));
+  if (int rc = observer_now(h, host.size(), host.data(), [&](u64* out) { return census_launch(h, part, rec, out, maxsub); })) return rc;
   memcpy(hdr, host.data(), sizeof *hdr);
   const u32 stored = (u32)host[CH_STORED];
   if (stored) memcpy(recs, host.data() + SIM_CENSUS_WORDS, (size_t)stored * sizeof *recs);

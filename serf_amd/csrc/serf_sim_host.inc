@@ -34,6 +34,7 @@ struct SplitArr {
   LazyPlanes lz;
 };
 enum { SP_VIEW = 0, SP_EV = 1, SP_Q = 2, SP_N = 3 };  // (the order of SIM_ARR_VIEW .. SIM_ARR_QRING and of the image's sections)
+enum { OB_SERIES = 0, OB_CENSUS = 1, OB_ROLL = 2, OB_LEDGER = 3, OB_N = 4 };  // the periodic observers, in the order their samples follow a tick on the stream
 // Function-local device scratch: freed when it goes out of scope — behind whatever stream synchronisation stands before that.
 template <typename T>
 struct DevScratch {
@@ -165,30 +166,15 @@ struct sim_handle {
   u64 ev_hi = 1, q_hi = 1;
   u32* deep_seen = nullptr;  // pinned: the longest deep list any launch has had (deep_queue_kernel keeps it; sizes that kernel's grid)
   struct TrackState* trk = nullptr;  // device-resident trackers (serf_sim_track.inc); null until the first sim_track_add
-  struct SeriesState* ser = nullptr;  // device-resident time series (serf_sim_series.inc); null unless one is running
-  struct CensusState* cen = nullptr;  // membership census (serf_sim_census.inc); null unless one is running
-  struct RollState* rol = nullptr;  // observer roll (serf_sim_roll.inc); null unless one is running
-  struct LedgerState* led = nullptr;  // rumour ledger (serf_sim_ledger.inc); null unless one is running
+  struct Observer* obs[OB_N] = {};  // the periodic observers (the frame at the end of this file); an entry is null unless its observer is running
   sim_handle() = default;
   sim_handle(const sim_handle&) = delete;
   sim_handle& operator=(const sim_handle&) = delete;
-  ~sim_handle();  // (serf_sim_api.inc, behind the observers' hooks)
+  ~sim_handle();  // (at the end of this file, behind the observers' frame)
 };
 // serf_sim_track.inc: the hooks of sim_step_end / ~sim_handle (called only when h->trk)
 static int track_step_end(sim_handle* h);
 static void track_destroy(sim_handle* h);
-// serf_sim_series.inc: likewise (called only when h->ser)
-static int series_step_end(sim_handle* h);
-static void series_destroy(sim_handle* h);
-// serf_sim_census.inc: likewise (called only when h->cen)
-static int census_step_end(sim_handle* h);
-static void census_destroy(sim_handle* h);
-// serf_sim_roll.inc: likewise (called only when h->rol)
-static int roll_step_end(sim_handle* h);
-static void roll_destroy(sim_handle* h);
-// serf_sim_ledger.inc: likewise (called only when h->led)
-static int ledger_step_end(sim_handle* h);
-static void ledger_destroy(sim_handle* h);
 
 #define HCHECK(x)                                                                        \
   do {                                                                                   \
@@ -347,30 +333,6 @@ static int rings_need(sim_handle* h) {
   int rc = lazy_need(h, h->sp[SP_EV].lz, h->d.X + h->ev_hi + 2);  // (rows 0 .. X-1: the overflow rows)
   return rc ? rc : lazy_need(h, h->sp[SP_Q].lz, h->d.X + h->q_hi + 2);
 }
-// Everything the handle holds, whatever sim_create, sim_exchange_init or an observer got as far as setting up.  Nothing is given back
-// while a stream may still use it: all three streams first.
-sim_handle::~sim_handle() {
-  (void)hipStreamSynchronize(stream);
-  if (xstream) (void)hipStreamSynchronize(xstream);
-  if (rf_stream) (void)hipStreamSynchronize(rf_stream);
-  if (trk) track_destroy(this);
-  if (ser) series_destroy(this);
-  if (cen) census_destroy(this);
-  if (rol) roll_destroy(this);
-  if (led) ledger_destroy(this);
-  if (xcomm) (void)ncclCommDestroy(xcomm);
-  if (xstream) (void)hipStreamDestroy(xstream);
-  if (rf_stream) (void)hipStreamDestroy(rf_stream);
-  for (hipEvent_t e : {xev_go, xev_done, xh_ev[0], xh_ev[1], xh_ev[2], xh_ev[3], rf_done[0], rf_done[1], rf_done[2], rf_go[0], rf_go[1],
-                       sreq_ev[0], sreq_ev[1], sreq_ev[2]})
-    if (e) (void)hipEventDestroy(e);
-  for (auto& pr : prof) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  for (void* p : {(void*)xh_host, (void*)sreq_host[0], (void*)sreq_host[1], (void*)sreq_host[2], (void*)xflag, (void*)deep_seen})
-    if (p) (void)hipHostFree(p);
-  if (d_pp) (void)hipFree(d_pp);
-  for (void* p : allocs) (void)hipFree(p);
-  for (SplitArr& A : sp) lazy_release(A.lz);
-}
 #define EV_CAP (1u << 20)
 
 // ---- what the observers share on the host (the device part: serf_sim_observe.inc; it stands here because it needs the handle) ----
@@ -423,4 +385,96 @@ static int sampler_read(sim_handle* h, const Sampler& S, u32 first, u32 n, void*
 static void sampler_close(Sampler& S) {  // (the caller has waited for the samples still enqueued)
   if (S.d_buf) (void)hipFree(S.d_buf);
   S.d_buf = nullptr;
+}
+
+// ---- the periodic observers' frame: series, census, roll and ledger differ in their kernels and in nothing below ----
+// A periodic observer while it runs: its samples and, in the struct derived from it, the scratch and the parameters of its kernels.
+struct Observer {
+  Sampler smp;
+  virtual ~Observer() { sampler_close(smp); }  // (the caller has waited for the samples still enqueued)
+  // one sample of the state the stream will be in when it gets here, enqueued into out[smp.stride_words]
+  virtual int sample(sim_handle* h, u64* out) = 0;
+};
+static void observer_destroy(sim_handle* h, u32 k) {  // (null: nothing runs)
+  delete h->obs[k];
+  h->obs[k] = nullptr;
+}
+// sim_<observer>_start.  `fresh` is the observer as far as the host alone can build it (taken over here); check() judges the observer's own
+// arguments, setup() gets its device scratch.  Everything is built off the handle and installed when all of it has succeeded: a start that
+// fails leaves no observer.  The order of the checks is the ABI's: bad arguments are SIM_EINVAL before "already running" is SIM_ESTATE.
+template <typename Check, typename Setup>
+static int observer_start(sim_handle* h, u32 k, Observer* fresh, u32 max_samples, u32 first_tick, u32 period, u32 capacity,
+                          size_t stride_words, Check check, Setup setup) {
+  std::unique_ptr<Observer> o(fresh);
+  if (int rc = observer_usable(h)) return rc;
+  if (!period || !capacity || capacity > max_samples) return SIM_EINVAL;
+  if (int rc = check()) return rc;
+  if (h->obs[k]) return SIM_ESTATE;
+  if (int rc = setup()) return rc;
+  if (int rc = sampler_open(h, o->smp, first_tick, period, capacity, stride_words)) return rc;
+  h->obs[k] = o.release();
+  return SIM_OK;
+}
+static int observer_count(const sim_handle* h, u32 k, u32* taken, u32* dropped) {
+  if (int rc = observer_usable(h)) return rc;
+  if (!taken || !dropped) return SIM_EINVAL;
+  sampler_count(h->obs[k] ? &h->obs[k]->smp : nullptr, taken, dropped);
+  return SIM_OK;
+}
+static int observer_read(sim_handle* h, u32 k, u32 first, u32 n, void* out, size_t cap_words, u32* n_out) {
+  if (int rc = observer_usable(h)) return rc;
+  if (!out || !n_out) return SIM_EINVAL;
+  if (!h->obs[k]) return SIM_ESTATE;
+  return sampler_read(h, h->obs[k]->smp, first, n, out, cap_words, n_out);
+}
+static int observer_stop(sim_handle* h, u32 k) {
+  if (int rc = observer_usable(h)) return rc;
+  if (!h->obs[k]) return SIM_ESTATE;
+  HCHECK(hipStreamSynchronize(h->stream));  // (samples still enqueued write into the buffers)
+  observer_destroy(h, k);
+  return SIM_OK;
+}
+// sim_step_end: tick h->tick - 1 has been enqueued; the samples of it that are due follow it on the stream
+static int observers_step_end(sim_handle* h) {
+  for (Observer* o : h->obs) {
+    u64* slot = o ? sampler_slot(h, o->smp) : nullptr;
+    if (!slot) continue;
+    if (int rc = o->sample(h, slot)) return rc;
+    sampler_commit(o->smp);
+  }
+  return SIM_OK;
+}
+// The tail of sim_<observer>_now: launch(out) enqueues one sample into device memory of `words` words, which then comes to host[words].
+// The stream is synchronised before any scratch is freed — `out` here, the caller's behind this call — also when the launch failed.
+template <typename Launch>
+static int observer_now(sim_handle* h, size_t words, u64* host, Launch launch) {
+  DevScratch<u64> out;
+  int rc = out.alloc(words);
+  if (rc == SIM_OK) rc = launch(out.get());
+  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == SIM_OK) rc = SIM_EDEVICE;
+  if (rc != SIM_OK) return rc;
+  HCHECK(hipMemcpy(host, out.get(), words * 8, hipMemcpyDeviceToHost));
+  return SIM_OK;
+}
+
+// Everything the handle holds, whatever sim_create, sim_exchange_init or an observer got as far as setting up.  Nothing is given back
+// while a stream may still use it: all three streams first.
+sim_handle::~sim_handle() {
+  (void)hipStreamSynchronize(stream);
+  if (xstream) (void)hipStreamSynchronize(xstream);
+  if (rf_stream) (void)hipStreamSynchronize(rf_stream);
+  if (trk) track_destroy(this);
+  for (u32 k = 0; k < OB_N; ++k) observer_destroy(this, k);
+  if (xcomm) (void)ncclCommDestroy(xcomm);
+  if (xstream) (void)hipStreamDestroy(xstream);
+  if (rf_stream) (void)hipStreamDestroy(rf_stream);
+  for (hipEvent_t e : {xev_go, xev_done, xh_ev[0], xh_ev[1], xh_ev[2], xh_ev[3], rf_done[0], rf_done[1], rf_done[2], rf_go[0], rf_go[1],
+                       sreq_ev[0], sreq_ev[1], sreq_ev[2]})
+    if (e) (void)hipEventDestroy(e);
+  for (auto& pr : prof) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+  for (void* p : {(void*)xh_host, (void*)sreq_host[0], (void*)sreq_host[1], (void*)sreq_host[2], (void*)xflag, (void*)deep_seen})
+    if (p) (void)hipHostFree(p);
+  if (d_pp) (void)hipFree(d_pp);
+  for (void* p : allocs) (void)hipFree(p);
+  for (SplitArr& A : sp) lazy_release(A.lz);
 }

@@ -22,7 +22,7 @@
 //   ledger_fold_kernel   one wave per word of the sample: folds its row (fold_row), or takes the entry's identity from the table, its
 //                        reach from the reach pass's counters, and writes the word into the sample's slot
 // Their order is the stream's.  The host knows every sampled tick in advance: it passes the slot to the launches and reads nothing back.
-// A handle without a started ledger never gets here (sim_step_end tests one pointer).
+// A handle without a started ledger never gets here (sim_step_end finds its entry of the observers' table null).
 #include "../../include/serf_sim_ledger.h"
 
 static_assert(sizeof(sim_ledger_entry) == 16 && SIM_LEDGER_MAX == SIM_CONV_MAX && SIM_LEDGER_MAX == 64u && SIM_LEDGER_HEADER_WORDS == 8u &&
@@ -207,10 +207,6 @@ struct LedScratch {
   ConvSet cs;               // the entries of kinds 1-4, as the reach pass takes them
   u32 n = 0;
 };
-struct LedgerState {
-  LedScratch scr;
-  Sampler smp;  // samples of 8 + 8 n words
-};
 static inline size_t ledger_stride(u32 n) { return SIM_LEDGER_HEADER_WORDS + (size_t)n * SIM_LEDGER_ENTRY_WORDS; }  // words of a sample
 
 // the entries checked and put into the kernels' form; touches nothing but t and cs
@@ -261,13 +257,6 @@ static int ledger_prepare(sim_handle* h, const sim_ledger_entry* e, u32 n, LedSc
   HCHECK(hipMemcpy(s.d_tab.get(), &t, sizeof t, hipMemcpyHostToDevice));
   return SIM_OK;
 }
-static void ledger_destroy(sim_handle* h) {
-  LedgerState* s = h->led;
-  if (!s) return;
-  sampler_close(s->smp);
-  delete s;
-  h->led = nullptr;
-}
 // one ledger sample of the state the stream will be in when it gets here, into out[ledger_stride(n)]
 static int ledger_launch(sim_handle* h, const LedScratch& s, u64* out) {
   const Dev& d = h->d;
@@ -291,72 +280,41 @@ static int ledger_launch(sim_handle* h, const LedScratch& s, u64* out) {
   HCHECK(hipGetLastError());
   return SIM_OK;
 }
-// sim_step_end: tick h->tick - 1 has been enqueued; a sample of it follows it on the stream
-static int ledger_step_end(sim_handle* h) {
-  LedgerState* s = h->led;
-  u64* slot = sampler_slot(h, s->smp);
-  if (!slot) return SIM_OK;
-  if (int rc = ledger_launch(h, s->scr, slot)) return rc;
-  sampler_commit(s->smp);
-  return SIM_OK;
-}
+struct LedgerState : Observer {  // samples of 8 + 8 n words
+  LedScratch scr;
+  int sample(sim_handle* h, u64* out) override { return ledger_launch(h, scr, out); }
+};
 
 extern "C" {
 
 uint32_t sim_ledger_version(void) { return SIM_LEDGER_VERSION; }
 
 int sim_ledger_start(sim_handle* h, const sim_ledger_entry* e, uint32_t n, uint32_t first_tick, uint32_t period, uint32_t capacity) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!period || !capacity || capacity > SIM_LEDGER_MAX_SAMPLES) return SIM_EINVAL;
-  {
+  LedgerState* s = new LedgerState();
+  const auto check = [&] {
     LedTab t;
     ConvSet cs;
-    if (int rc = ledger_check(h, e, n, t, cs)) return rc;
-  }
-  if (h->led) return SIM_ESTATE;
-  std::unique_ptr<LedgerState> s(new LedgerState());
-  if (int rc = ledger_prepare(h, e, n, s->scr)) return rc;
-  if (sampler_open(h, s->smp, first_tick, period, capacity, ledger_stride(n)) != SIM_OK) return SIM_ENOMEM;
-  h->led = s.release();
-  return SIM_OK;
+    return ledger_check(h, e, n, t, cs);
+  };
+  return observer_start(h, OB_LEDGER, s, SIM_LEDGER_MAX_SAMPLES, first_tick, period, capacity, ledger_stride(n), check,
+                        [&] { return ledger_prepare(h, e, n, s->scr); });
 }
 
-int sim_ledger_count(const sim_handle* h, uint32_t* taken, uint32_t* dropped) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!taken || !dropped) return SIM_EINVAL;
-  sampler_count(h->led ? &h->led->smp : nullptr, taken, dropped);
-  return SIM_OK;
-}
+int sim_ledger_count(const sim_handle* h, uint32_t* taken, uint32_t* dropped) { return observer_count(h, OB_LEDGER, taken, dropped); }
 
 int sim_ledger_read(sim_handle* h, uint32_t first, uint32_t n, uint64_t* out, size_t cap_words, uint32_t* n_out) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!out || !n_out) return SIM_EINVAL;
-  if (!h->led) return SIM_ESTATE;
-  return sampler_read(h, h->led->smp, first, n, out, cap_words, n_out);
+  return observer_read(h, OB_LEDGER, first, n, out, cap_words, n_out);
 }
 
-int sim_ledger_stop(sim_handle* h) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!h->led) return SIM_ESTATE;
-  HCHECK(hipStreamSynchronize(h->stream));  // (samples still enqueued write into the buffers)
-  ledger_destroy(h);
-  return SIM_OK;
-}
+int sim_ledger_stop(sim_handle* h) { return observer_stop(h, OB_LEDGER); }
 
 int sim_ledger_now(sim_handle* h, const sim_ledger_entry* e, uint32_t n, uint64_t* out) {
   if (int rc = observer_usable(h)) return rc;
   if (!out) return SIM_EINVAL;
   // scratch of its own: a running ledger's table and partial matrix are those of ITS entries, and its samples still enqueued use them
   LedScratch own;
-  DevScratch<u64> d_out;
-  int rc = ledger_prepare(h, e, n, own);
-  if (rc == SIM_OK) rc = d_out.alloc(ledger_stride(n));
-  if (rc != SIM_OK) return rc;
-  rc = ledger_launch(h, own, d_out.get());
-  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == SIM_OK) rc = SIM_EDEVICE;  // (also before the scratch goes)
-  if (rc != SIM_OK) return rc;
-  HCHECK(hipMemcpy(out, d_out.get(), ledger_stride(n) * 8, hipMemcpyDeviceToHost));
-  return SIM_OK;
+  if (int rc = ledger_prepare(h, e, n, own)) return rc;
+  return observer_now(h, ledger_stride(n), out, [&](u64* d_out) { return ledger_launch(h, own, d_out); });
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@
 //                        workgroups' candidate lists (each sorted: the largest key of a list below the last one chosen is the first
 //                        below it) and writes the listed records, zeroing what stays unused
 // Their order is the stream's.  The host knows every sampled tick in advance: it passes the sample's place to the launches and reads nothing back.
-// A handle without a started roll never gets here (sim_step_end tests one pointer).
+// A handle without a started roll never gets here (sim_step_end finds its entry of the observers' table null).
 #include "../../include/serf_sim_roll.h"
 
 static_assert(sizeof(sim_roll_node) == 64 && sizeof(sim_roll_header) == 256 && SIM_ROLL_NODE_WORDS == 8u && SIM_ROLL_HEADER_WORDS == 32u,
@@ -262,11 +262,6 @@ struct RollScratch {
   DevScratch<u64> d_part;           // [SIM_ROLL_HEADER_WORDS][G]
   DevScratch<u64> d_ckey, d_crec2;  // [G][top_k], [G][top_k][SIM_ROLL_NODE_WORDS]
 };
-struct RollState {
-  RollScratch scr;
-  Sampler smp;  // samples of SIM_ROLL_HEADER_WORDS + top_k * SIM_ROLL_NODE_WORDS words
-  u32 top_k = 0, rank_by = 0;
-};
 static inline u32 roll_groups(const sim_handle* h) { return (h->d.Nl + BLOCK - 1u) / BLOCK; }
 static inline size_t roll_stride(u32 top_k) { return SIM_ROLL_HEADER_WORDS + (size_t)top_k * SIM_ROLL_NODE_WORDS; }  // words of a sample
 static inline bool roll_args_ok(u32 top_k, u32 rank_by) { return top_k >= 1u && top_k <= SIM_ROLL_TOP_MAX && rank_by <= SIM_ROLL_BY_MISSED; }
@@ -278,23 +273,9 @@ static int roll_scratch(const sim_handle* h, RollScratch& s, u32 top_k) {
   if (int rc = s.d_ckey.alloc(G * top_k)) return rc;
   return s.d_crec2.alloc(G * top_k * SIM_ROLL_NODE_WORDS);
 }
-static void roll_destroy(sim_handle* h) {
-  RollState* s = h->rol;
-  if (!s) return;
-  sampler_close(s->smp);
-  delete s;
-  h->rol = nullptr;
-}
 // one roll of the state the stream will be in when it gets here, into out[roll_stride(top_k)]; nodes: null, or [N] records
 static int roll_launch(sim_handle* h, const RollScratch& s, u64* out, u64* nodes, u32 top_k, u32 rank_by) {
-  CenDevP c;
-  c.view = h->d.view; c.subject_of = h->d.subject_of; c.upmap = h->d.upmap;
-  c.N = h->d.N; c.Nl = h->d.Nl;
-  c.part = s.d_cpart.get(); c.rec = s.d_crec.get(); c.out = nullptr;
-  c.S = census_segments(h);
-  c.bound = std::min(h->n_slots, h->d.A);  // the host hands the slots out itself, in the stream's order: none beyond its high-water mark is in use
-  c.maxsub = 0;
-  c.now = (u32)h->tick;
+  const CenDevP c = census_records(h, s.d_cpart.get(), s.d_crec.get(), nullptr, 0);
   RollDevP p;
   p.view = c.view; p.subject_of = c.subject_of; p.upmap = c.upmap;
   p.rec = c.rec; p.part = s.d_part.get(); p.ckey = s.d_ckey.get(); p.crec = s.d_crec2.get();
@@ -304,82 +285,49 @@ static int roll_launch(sim_handle* h, const RollScratch& s, u64* out, u64* nodes
   p.bound = c.bound;
   p.top_k = top_k; p.rank_by = rank_by;
   p.now = c.now;
-  if (c.bound) {
-    census_count_kernel<<<c.bound * c.S, BLOCK, 0, h->stream>>>(c);
-    census_fold_kernel<<<(c.bound + BLOCK / 64 - 1) / (BLOCK / 64), BLOCK, 0, h->stream>>>(c);
-  }
   roll_count_kernel<<<p.G, BLOCK, 0, h->stream>>>(p);
   roll_fold_kernel<<<1, BLOCK, 0, h->stream>>>(p);
   HCHECK(hipGetLastError());
   return SIM_OK;
 }
-// sim_step_end: tick h->tick - 1 has been enqueued; a sample of it follows it on the stream
-static int roll_step_end(sim_handle* h) {
-  RollState* s = h->rol;
-  u64* slot = sampler_slot(h, s->smp);
-  if (!slot) return SIM_OK;
-  if (int rc = roll_launch(h, s->scr, slot, nullptr, s->top_k, s->rank_by)) return rc;
-  sampler_commit(s->smp);
-  return SIM_OK;
-}
+struct RollState : Observer {  // samples of SIM_ROLL_HEADER_WORDS + top_k * SIM_ROLL_NODE_WORDS words
+  RollScratch scr;
+  u32 top_k = 0, rank_by = 0;
+  int sample(sim_handle* h, u64* out) override { return roll_launch(h, scr, out, nullptr, top_k, rank_by); }
+};
 
 extern "C" {
 
 uint32_t sim_roll_version(void) { return SIM_ROLL_VERSION; }
 
 int sim_roll_start(sim_handle* h, uint32_t first_tick, uint32_t period, uint32_t capacity, uint32_t top_k, uint32_t rank_by) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!period || !capacity || capacity > SIM_ROLL_MAX_SAMPLES || !roll_args_ok(top_k, rank_by)) return SIM_EINVAL;
-  if (h->rol) return SIM_ESTATE;
   RollState* s = new RollState();
-  h->rol = s;
   s->top_k = top_k;
   s->rank_by = rank_by;
-  if (roll_scratch(h, s->scr, top_k) != SIM_OK || sampler_open(h, s->smp, first_tick, period, capacity, roll_stride(top_k)) != SIM_OK) {
-    (void)hipGetLastError();
-    roll_destroy(h);
-    return SIM_ENOMEM;
-  }
-  return SIM_OK;
+  return observer_start(h, OB_ROLL, s, SIM_ROLL_MAX_SAMPLES, first_tick, period, capacity, roll_stride(top_k),
+                        [&] { return roll_args_ok(top_k, rank_by) ? SIM_OK : SIM_EINVAL; }, [&] { return roll_scratch(h, s->scr, top_k); });
 }
 
-int sim_roll_count(const sim_handle* h, uint32_t* taken, uint32_t* dropped) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!taken || !dropped) return SIM_EINVAL;
-  sampler_count(h->rol ? &h->rol->smp : nullptr, taken, dropped);
-  return SIM_OK;
-}
+int sim_roll_count(const sim_handle* h, uint32_t* taken, uint32_t* dropped) { return observer_count(h, OB_ROLL, taken, dropped); }
 
 int sim_roll_read(sim_handle* h, uint32_t first, uint32_t n, uint64_t* out, size_t cap_words, uint32_t* n_out) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!out || !n_out) return SIM_EINVAL;
-  if (!h->rol) return SIM_ESTATE;
-  return sampler_read(h, h->rol->smp, first, n, out, cap_words, n_out);
+  return observer_read(h, OB_ROLL, first, n, out, cap_words, n_out);
 }
 
-int sim_roll_stop(sim_handle* h) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!h->rol) return SIM_ESTATE;
-  HCHECK(hipStreamSynchronize(h->stream));  // (samples still enqueued write into the buffers)
-  roll_destroy(h);
-  return SIM_OK;
-}
+int sim_roll_stop(sim_handle* h) { return observer_stop(h, OB_ROLL); }
 
 int sim_roll_now(sim_handle* h, uint32_t top_k, uint32_t rank_by, sim_roll_header* hdr, sim_roll_node* top, sim_roll_node* nodes) {
   if (int rc = observer_usable(h)) return rc;
   if (!hdr || !top || !roll_args_ok(top_k, rank_by)) return SIM_EINVAL;
   // scratch of its own: a running roll's candidate arrays are sized for ITS top_k, and its samples still enqueued use them
   RollScratch own;
-  DevScratch<u64> out, d_nodes;
+  DevScratch<u64> d_nodes;
   std::vector<u64> host(roll_stride(top_k));
   int rc = roll_scratch(h, own, top_k);
-  if (rc == SIM_OK) rc = out.alloc(host.size());
   if (rc == SIM_OK && nodes) rc = d_nodes.alloc((size_t)h->d.N * SIM_ROLL_NODE_WORDS);
   if (rc != SIM_OK) return rc;
-  rc = roll_launch(h, own, out.get(), nodes ? d_nodes.get() : nullptr, top_k, rank_by);
-  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == SIM_OK) rc = SIM_EDEVICE;  // (also before the scratch goes)
+  rc = observer_now(h, host.size(), host.data(), [&](u64* out) { return roll_launch(h, own, out, nodes ? d_nodes.get() : nullptr, top_k, rank_by); });
   if (rc != SIM_OK) return rc;
-  HCHECK(hipMemcpy(host.data(), out.get(), host.size() * 8, hipMemcpyDeviceToHost));
   if (nodes) HCHECK(hipMemcpy(nodes, d_nodes.get(), (size_t)h->d.N * sizeof *nodes, hipMemcpyDeviceToHost));
   memcpy(hdr, host.data(), sizeof *hdr);
   memcpy(top, host.data() + SIM_ROLL_HEADER_WORDS, (size_t)top_k * sizeof *top);

@@ -8,7 +8,7 @@
 //                         throughout, no atomics on global memory, nothing to zero
 //   series_fold_kernel    one wave per word: adds its row up (or takes its min / max), writes the word into the sample's slot
 // Their order is the stream's.  The host knows every sampled tick in advance: it passes the slot to the launch and reads nothing back.
-// A handle without a started series never gets here (sim_step_end tests one pointer).
+// A handle without a started series never gets here (sim_step_end finds its entry of the observers' table null).
 #include "../../include/serf_sim_series.h"
 
 static_assert(sizeof(sim_series_sample) == 512 && SIM_SERIES_WORDS == 64u, "layout of include/serf_sim_series.h");
@@ -198,78 +198,40 @@ __global__ __launch_bounds__(BLOCK) void series_fold_kernel(SerDevP p) {
 }
 
 // ---- host ----
-struct SeriesState {
-  u64* d_part = nullptr;  // [SIM_SERIES_WORDS][SER_GRID]
-  Sampler smp;            // samples of SIM_SERIES_WORDS words
+struct SeriesState : Observer {  // samples of SIM_SERIES_WORDS words
+  DevScratch<u64> d_part;  // [SIM_SERIES_WORDS][SER_GRID]
+  int sample(sim_handle* h, u64* out) override {
+    const Dev& d = h->d;
+    SerDevP p;
+    p.part = d_part.get();
+    p.out = out;
+    p.G = (u32)std::min<size_t>(((size_t)d.Nl + BLOCK - 1) / BLOCK, SER_GRID);
+    p.now = (u32)h->tick;
+    p.cur = (u32)(h->tick & 1);
+    p.nslot = d.rfan ? d.f : h->prev.feff;  // (h->prev: the parameters of the tick that just ended, the one that sent the packets)
+    series_sample_kernel<<<p.G, BLOCK, 0, h->stream>>>(d, p);
+    series_fold_kernel<<<SIM_SERIES_WORDS / (BLOCK / 64), BLOCK, 0, h->stream>>>(p);
+    HCHECK(hipGetLastError());
+    return SIM_OK;
+  }
 };
-
-static void series_destroy(sim_handle* h) {
-  SeriesState* s = h->ser;
-  if (!s) return;
-  if (s->d_part) (void)hipFree(s->d_part);
-  sampler_close(s->smp);
-  delete s;
-  h->ser = nullptr;
-}
-// sim_step_end: tick h->tick - 1 has been enqueued; a sample of it follows it on the stream
-static int series_step_end(sim_handle* h) {
-  SeriesState* s = h->ser;
-  u64* slot = sampler_slot(h, s->smp);
-  if (!slot) return SIM_OK;
-  const Dev& d = h->d;
-  SerDevP p;
-  p.part = s->d_part;
-  p.out = slot;
-  p.G = (u32)std::min<size_t>(((size_t)d.Nl + BLOCK - 1) / BLOCK, SER_GRID);
-  p.now = (u32)h->tick;
-  p.cur = (u32)(h->tick & 1);
-  p.nslot = d.rfan ? d.f : h->prev.feff;  // (h->prev: the parameters of the tick that just ended, the one that sent the packets)
-  series_sample_kernel<<<p.G, BLOCK, 0, h->stream>>>(d, p);
-  series_fold_kernel<<<SIM_SERIES_WORDS / (BLOCK / 64), BLOCK, 0, h->stream>>>(p);
-  HCHECK(hipGetLastError());
-  sampler_commit(s->smp);
-  return SIM_OK;
-}
 
 extern "C" {
 
 uint32_t sim_series_version(void) { return SIM_SERIES_VERSION; }
 
 int sim_series_start(sim_handle* h, uint32_t first_tick, uint32_t period, uint32_t capacity) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!period || !capacity || capacity > SIM_SERIES_MAX_SAMPLES) return SIM_EINVAL;
-  if (h->ser) return SIM_ESTATE;
   SeriesState* s = new SeriesState();
-  h->ser = s;
-  if (hipMalloc((void**)&s->d_part, (size_t)SIM_SERIES_WORDS * SER_GRID * 8) != hipSuccess ||
-      sampler_open(h, s->smp, first_tick, period, capacity, SIM_SERIES_WORDS) != SIM_OK) {
-    (void)hipGetLastError();
-    series_destroy(h);
-    return SIM_ENOMEM;
-  }
-  return SIM_OK;
+  return observer_start(h, OB_SERIES, s, SIM_SERIES_MAX_SAMPLES, first_tick, period, capacity, SIM_SERIES_WORDS,
+                        [] { return SIM_OK; }, [&] { return s->d_part.alloc((size_t)SIM_SERIES_WORDS * SER_GRID); });
 }
 
-int sim_series_count(const sim_handle* h, uint32_t* taken, uint32_t* dropped) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!taken || !dropped) return SIM_EINVAL;
-  sampler_count(h->ser ? &h->ser->smp : nullptr, taken, dropped);
-  return SIM_OK;
-}
+int sim_series_count(const sim_handle* h, uint32_t* taken, uint32_t* dropped) { return observer_count(h, OB_SERIES, taken, dropped); }
 
 int sim_series_read(sim_handle* h, uint32_t first, uint32_t n, sim_series_sample* out, uint32_t* n_out) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!out || !n_out) return SIM_EINVAL;
-  if (!h->ser) return SIM_ESTATE;
-  return sampler_read(h, h->ser->smp, first, n, out, ~(size_t)0, n_out);
+  return observer_read(h, OB_SERIES, first, n, out, ~(size_t)0, n_out);
 }
 
-int sim_series_stop(sim_handle* h) {
-  if (int rc = observer_usable(h)) return rc;
-  if (!h->ser) return SIM_ESTATE;
-  HCHECK(hipStreamSynchronize(h->stream));  // (samples still enqueued write into the buffers)
-  series_destroy(h);
-  return SIM_OK;
-}
+int sim_series_stop(sim_handle* h) { return observer_stop(h, OB_SERIES); }
 
 }  // extern "C"

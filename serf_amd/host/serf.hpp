@@ -224,11 +224,8 @@ class Cluster {
   void series_start(uint32_t first_tick = 0, uint32_t period = 1, uint32_t capacity = 1u << 16) {
     check(sim_series_start(h_, first_tick, period, capacity), "sim_series_start");
   }
-  std::pair<uint32_t, uint32_t> series_count() const {  // (samples taken, dropped with the buffer full); waits for nothing
-    uint32_t t = 0, d = 0;
-    check(sim_series_count(h_, &t, &d), "sim_series_count");
-    return {t, d};
-  }
+  // (samples taken, dropped with the buffer full); waits for nothing
+  std::pair<uint32_t, uint32_t> series_count() const { return sample_count(sim_series_count, "sim_series_count"); }
   std::vector<sim_series_sample> series_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
     if (n == 0xFFFFFFFFu) { const uint32_t t = series_count().first; n = t > first ? t - first : 0; }
     std::vector<sim_series_sample> out(n ? n : 1);
@@ -249,25 +246,11 @@ class Cluster {
     check(sim_census_start(h_, first_tick, period, capacity, max_subjects), "sim_census_start");
     census_max_ = max_subjects;
   }
-  std::pair<uint32_t, uint32_t> census_count() const {  // (samples taken, dropped with the buffer full); waits for nothing
-    uint32_t t = 0, d = 0;
-    check(sim_census_count(h_, &t, &d), "sim_census_count");
-    return {t, d};
-  }
+  // (samples taken, dropped with the buffer full); waits for nothing
+  std::pair<uint32_t, uint32_t> census_count() const { return sample_count(sim_census_count, "sim_census_count"); }
   std::vector<CensusSample> census_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
-    if (n == 0xFFFFFFFFu) { const uint32_t t = census_count().first; n = t > first ? t - first : 0; }
-    const size_t stride = ((size_t)census_max_ + 1) * SIM_CENSUS_WORDS;
-    std::vector<uint64_t> words((n ? n : 1) * stride);
-    uint32_t got = 0;
-    check(sim_census_read(h_, first, n, words.data(), words.size(), &got), "sim_census_read");
-    std::vector<CensusSample> out(got);
-    for (uint32_t i = 0; i < got; ++i) {
-      const uint64_t* w = words.data() + i * stride;
-      std::memcpy(&out[i].header, w, sizeof(sim_census_header));
-      out[i].subjects.resize((size_t)out[i].header.w[3]);
-      if (!out[i].subjects.empty()) std::memcpy(out[i].subjects.data(), w + SIM_CENSUS_WORDS, out[i].subjects.size() * sizeof(sim_census_subject));
-    }
-    return out;
+    return sample_read<CensusSample>(sim_census_count, sim_census_read, "sim_census", first, n, ((size_t)census_max_ + 1) * SIM_CENSUS_WORDS,
+                                     [](const uint64_t* w, CensusSample& s) { unpack(w, (size_t)w[3], s.header, s.subjects); });
   }
   void census_stop() { check(sim_census_stop(h_), "sim_census_stop"); }
   CensusSample census_now(uint32_t cap = 64) {  // the state the handle is in now, with or without a running census
@@ -291,25 +274,11 @@ class Cluster {
     check(sim_roll_start(h_, first_tick, period, capacity, top_k, rank_by), "sim_roll_start");
     roll_top_ = top_k;
   }
-  std::pair<uint32_t, uint32_t> roll_count() const {  // (samples taken, dropped with the buffer full); waits for nothing
-    uint32_t t = 0, d = 0;
-    check(sim_roll_count(h_, &t, &d), "sim_roll_count");
-    return {t, d};
-  }
+  // (samples taken, dropped with the buffer full); waits for nothing
+  std::pair<uint32_t, uint32_t> roll_count() const { return sample_count(sim_roll_count, "sim_roll_count"); }
   std::vector<RollSample> roll_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
-    if (n == 0xFFFFFFFFu) { const uint32_t t = roll_count().first; n = t > first ? t - first : 0; }
-    const size_t stride = SIM_ROLL_HEADER_WORDS + (size_t)roll_top_ * SIM_ROLL_NODE_WORDS;
-    std::vector<uint64_t> words((n ? n : 1) * stride);
-    uint32_t got = 0;
-    check(sim_roll_read(h_, first, n, words.data(), words.size(), &got), "sim_roll_read");
-    std::vector<RollSample> out(got);
-    for (uint32_t i = 0; i < got; ++i) {
-      const uint64_t* w = words.data() + i * stride;
-      std::memcpy(&out[i].header, w, sizeof(sim_roll_header));
-      out[i].top.resize((size_t)(out[i].header.w[3] & 0xFFFFFFFFu));
-      if (!out[i].top.empty()) std::memcpy(out[i].top.data(), w + SIM_ROLL_HEADER_WORDS, out[i].top.size() * sizeof(sim_roll_node));
-    }
-    return out;
+    return sample_read<RollSample>(sim_roll_count, sim_roll_read, "sim_roll", first, n, SIM_ROLL_HEADER_WORDS + (size_t)roll_top_ * SIM_ROLL_NODE_WORDS,
+                                   [](const uint64_t* w, RollSample& s) { unpack(w, (size_t)(w[3] & 0xFFFFFFFFu), s.header, s.top); });
   }
   void roll_stop() { check(sim_roll_stop(h_), "sim_roll_stop"); }
   // the state the handle is in now, with or without a running roll
@@ -333,20 +302,12 @@ class Cluster {
     check(sim_ledger_start(h_, e.data(), (uint32_t)e.size(), first_tick, period, capacity), "sim_ledger_start");
     ledger_n_ = (uint32_t)e.size();
   }
-  std::pair<uint32_t, uint32_t> ledger_count() const {  // (samples taken, dropped with the buffer full); waits for nothing
-    uint32_t t = 0, d = 0;
-    check(sim_ledger_count(h_, &t, &d), "sim_ledger_count");
-    return {t, d};
-  }
+  // (samples taken, dropped with the buffer full); waits for nothing
+  std::pair<uint32_t, uint32_t> ledger_count() const { return sample_count(sim_ledger_count, "sim_ledger_count"); }
   std::vector<LedgerSample> ledger_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
-    if (n == 0xFFFFFFFFu) { const uint32_t t = ledger_count().first; n = t > first ? t - first : 0; }
-    const size_t stride = SIM_LEDGER_HEADER_WORDS + (size_t)ledger_n_ * SIM_LEDGER_ENTRY_WORDS;
-    std::vector<uint64_t> words((n ? n : 1) * stride);
-    uint32_t got = 0;
-    check(sim_ledger_read(h_, first, n, words.data(), words.size(), &got), "sim_ledger_read");
-    std::vector<LedgerSample> out(got);
-    for (uint32_t i = 0; i < got; ++i) ledger_unpack(words.data() + i * stride, ledger_n_, out[i]);
-    return out;
+    const uint32_t ne = ledger_n_;
+    return sample_read<LedgerSample>(sim_ledger_count, sim_ledger_read, "sim_ledger", first, n, SIM_LEDGER_HEADER_WORDS + (size_t)ne * SIM_LEDGER_ENTRY_WORDS,
+                                     [ne](const uint64_t* w, LedgerSample& s) { unpack(w, ne, s.header, s.entries); });
   }
   void ledger_stop() { check(sim_ledger_stop(h_), "sim_ledger_stop"); }
   // the state the handle is in now, with or without a running ledger, for entries of its own
@@ -354,7 +315,7 @@ class Cluster {
     std::vector<uint64_t> words(SIM_LEDGER_HEADER_WORDS + (e.size() ? e.size() : 1) * SIM_LEDGER_ENTRY_WORDS);
     check(sim_ledger_now(h_, e.data(), (uint32_t)e.size(), words.data()), "sim_ledger_now");
     LedgerSample s;
-    ledger_unpack(words.data(), (uint32_t)e.size(), s);
+    unpack(words.data(), e.size(), s.header, s.entries);
     return s;
   }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
@@ -374,11 +335,31 @@ class Cluster {
   uint32_t census_max_ = 1;  // max_subjects of the running census: the stride of its samples
   uint32_t roll_top_ = 1;    // top_k of the running roll: likewise
   uint32_t ledger_n_ = 1;    // entries of the running ledger: likewise
-  static void ledger_unpack(const uint64_t* w, uint32_t n, LedgerSample& s) {
-    static_assert(sizeof(LedgerSample::Entry) == 8 * SIM_LEDGER_ENTRY_WORDS, "an entry's record is eight words");
-    std::memcpy(s.header, w, sizeof s.header);
-    s.entries.resize(n);
-    if (n) std::memcpy(s.entries.data(), w + SIM_LEDGER_HEADER_WORDS, (size_t)n * sizeof(LedgerSample::Entry));
+  static_assert(sizeof(LedgerSample::Entry) == 8 * SIM_LEDGER_ENTRY_WORDS, "an entry's record is eight words");
+  // what the four periodic observers share: the count, and "read n samples of `stride` words and unpack each"
+  std::pair<uint32_t, uint32_t> sample_count(int (*count)(const sim_handle*, uint32_t*, uint32_t*), const char* what) const {
+    uint32_t t = 0, d = 0;
+    check(count(h_, &t, &d), what);
+    return {t, d};
+  }
+  template <typename Sample, typename Unpack>
+  std::vector<Sample> sample_read(int (*count)(const sim_handle*, uint32_t*, uint32_t*),
+                                  int (*read)(sim_handle*, uint32_t, uint32_t, uint64_t*, size_t, uint32_t*), const std::string& group,
+                                  uint32_t first, uint32_t n, size_t stride, Unpack unpack_one) {
+    if (n == 0xFFFFFFFFu) { const uint32_t t = sample_count(count, (group + "_count").c_str()).first; n = t > first ? t - first : 0; }
+    std::vector<uint64_t> words((n ? n : 1) * stride);
+    uint32_t got = 0;
+    check(read(h_, first, n, words.data(), words.size(), &got), (group + "_read").c_str());
+    std::vector<Sample> out(got);
+    for (uint32_t i = 0; i < got; ++i) unpack_one(words.data() + i * stride, out[i]);
+    return out;
+  }
+  // a sample's words -> its header (the first sizeof(Header) bytes) and the n records behind it
+  template <typename Header, typename Rec>
+  static void unpack(const uint64_t* w, size_t n, Header& header, std::vector<Rec>& recs) {
+    std::memcpy(&header, w, sizeof header);
+    recs.resize(n);
+    if (n) std::memcpy(recs.data(), w + sizeof header / 8, n * sizeof(Rec));
   }
 };
 
