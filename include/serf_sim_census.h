@@ -18,6 +18,11 @@
  * images do not know it (sim_snapshot holds none, sim_restore leaves a running one as it is), and a handle without a
  * started census launches, allocates and synchronises nothing for it.
  *
+ * Checkpoints: sim_snapshot holds no census, sim_restore leaves a running one as it is.  It keeps the first tick and
+ * the period fixed when it was started, in absolute ticks: behind a restore to tick T its samples go on behind the
+ * ticks t >= T with (t - first) % period == 0, in the same buffer, and what fell between is neither taken nor
+ * counted as dropped.
+ *
  * SUBJECT: a node id that owns a view slot now (subject_of[slot] is a node).  A subject without a slot sits at its
  * baseline, where every observer agrees by construction: it is NOT in the census.  On a dense handle (view_slots == 0
  * or >= n_nodes) every node owns slot == id: the census covers all N subjects and a sample costs N * N entries —

@@ -16,6 +16,11 @@
  * copies the cluster sent.  A ledger adds no protocol state: digests, events, dumps, checkpoint images do not know it, and
  * a handle without a started ledger launches, allocates and synchronises nothing for it.
  *
+ * Checkpoints: sim_snapshot holds no ledger, sim_restore leaves a running one as it is.  It keeps the first tick and
+ * the period fixed when it was started, in absolute ticks: behind a restore to tick T its samples go on behind the
+ * ticks t >= T with (t - first) % period == 0, in the same buffer, and what fell between is neither taken nor
+ * counted as dropped.
+ *
  * An ENTRY names a record identity:
  *   kind   SIM_K_JOIN .. SIM_K_DEAD (1-7)
  *   key    JOIN / LEAVE / ALIVE / SUSPECT / DEAD: the subject (< n_nodes); EVENT / QUERY: the event key or query id, non-zero

@@ -19,6 +19,11 @@
  * checkpoint images do not know it (sim_snapshot holds none, sim_restore leaves a running one as it is), and a handle
  * without a started roll launches, allocates and synchronises nothing for it.
  *
+ * Checkpoints: sim_snapshot holds no roll, sim_restore leaves a running one as it is.  It keeps the first tick and
+ * the period fixed when it was started, in absolute ticks: behind a restore to tick T its samples go on behind the
+ * ticks t >= T with (t - first) % period == 0, in the same buffer, and what fell between is neither taken nor
+ * counted as dropped.
+ *
  * SUBJECT: a node id that owns a view slot now (subject_of[slot] is a node).  As in the census, a subject without a slot
  * sits at its baseline, where every observer agrees by construction: it is NOT in the roll.
  * OBSERVER: every running node (flags & SIM_RF_UP) of the handle, the subject itself included.

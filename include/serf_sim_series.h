@@ -15,6 +15,11 @@
  * digests, events, dumps and checkpoint images do not know it (sim_snapshot holds none, sim_restore leaves a running one
  * as it is), and a handle without a started series launches, allocates and synchronises nothing for it.
  *
+ * Checkpoints: sim_snapshot holds no series, sim_restore leaves a running one as it is.  It keeps the first tick and
+ * the period fixed when it was started, in absolute ticks: behind a restore to tick T its samples go on behind the
+ * ticks t >= T with (t - first) % period == 0, in the same buffer, and what fell between is neither taken nor
+ * counted as dropped.
+ *
  * Out of scope: sharded handles (shard_count > 1, SIM_CF_FORCE_SHARDED) — a sample needs the sums over ALL nodes; every
  * call below returns SIM_ESTATE on such a handle (vshards > 1 on a handle that holds every node is one handle and is
  * supported); counters that would need the handlers instrumented (serf.member.*, serf.events, serf.messages.received);

@@ -18,7 +18,10 @@
  *   - the count of every tick as a curve: only the latches, the peak and the last count are kept;
  *   - resolving a user event's / query's Lamport time on the device: the host passes it, as for sim_convergence
  *     (sim_stats_get(node).event_time / query_time BEFORE the call that originates it);
- *   - checkpoints: sim_snapshot does not hold trackers, sim_restore leaves the registered ones as they are.
+ *   - checkpoints: sim_snapshot does not hold trackers, sim_restore leaves the registered ones as they are.  A window
+ *     keeps the absolute ticks fixed at registration: a tracker whose window lies before the restored tick is never
+ *     evaluated and stays in state 0 until it is removed; one whose window straddles it is evaluated from the restored
+ *     tick to the window's end.
  */
 #ifndef SERF_SIM_TRACK_H
 #define SERF_SIM_TRACK_H
