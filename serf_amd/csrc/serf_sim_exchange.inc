@@ -141,7 +141,7 @@ int sim_exchange_chunk(sim_handle* h, uint32_t chunk) {
     // kernel nor the two gaps around it (14 + 4 + 10 us of every tick on one rank); the host reads the result two ticks later.
     hipStream_t hs = xs;
     if (inl && h->rf_stream) {
-      hipEvent_t ev = V == 1u ? h->sreq_wait[t % 3] : nullptr;
+      hipEvent_t ev = V == 1u ? tick_done_event(h, t) : nullptr;
       if (!ev) { HCHECK(hipEventRecord(h->xev_go, h->stream)); ev = h->xev_go; }
       HCHECK(hipStreamWaitEvent(h->rf_stream, ev, 0));
       hs = h->rf_stream;

@@ -158,7 +158,7 @@ struct sim_handle {
   hipStream_t rf_stream = nullptr;
   hipEvent_t rf_done[3] = {}, rf_go[2] = {};
   u64 rf_q[3] = {~0ull, ~0ull, ~0ull};
-  bool rf_sync = false, rf_lean = false;
+  bool rf_sync = false;
   // view entries and ring buckets on demand (SP_VIEW, SP_EV, SP_Q); ev_hi / q_hi: no node's event / query clock exceeds them (a clock
   // starts at 1, grows by one per user event / query somebody originates and is otherwise a maximum of clocks seen; a record or a clock
   // that comes in over the byte boundary raises the bound to its own time + 1) — so no record's Lamport time does
@@ -175,6 +175,12 @@ struct sim_handle {
 // serf_sim_track.inc: the hooks of sim_step_end / ~sim_handle (called only when h->trk)
 static int track_step_end(sim_handle* h);
 static void track_destroy(sim_handle* h);
+// serf_sim_step.inc: what sim_create, sim_snapshot, sim_restore and sim_exchange_chunk need of the per-tick path
+static int create_rf(sim_handle* h);
+static int sreq_take(sim_handle* h, u64 t, uint32_t* out, uint32_t cap_pairs, uint32_t* n_pairs);
+static int rfx_pack(sim_handle* h, u64 t, u32 c);
+static int rf_reset(sim_handle* h);
+static hipEvent_t tick_done_event(const sim_handle* h, u64 t);
 
 #define HCHECK(x)                                                                        \
   do {                                                                                   \
@@ -248,6 +254,8 @@ static int dalloc(sim_handle* h, T** p, size_t n) {
   *p = (T*)v;
   return SIM_OK;
 }
+#define DA(ptr, n) \
+  if (int rc_ = dalloc(h, &(ptr), (n))) return rc_;
 static inline int grid_for(size_t n) { return (int)std::min<size_t>((n + BLOCK - 1) / BLOCK, 8192); }
 // ---- LazyPlanes ----
 static hipMemAllocationProp lazy_prop(int device) {

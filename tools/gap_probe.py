@@ -45,7 +45,7 @@ if __name__ == "__main__":
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--profile", type=int, default=0)
     ap.add_argument("--lib", default=os.path.join(ROOT, "serf_amd", "csrc", "libserf_sim.so"))
-    ap.add_argument("--variants", nargs="*", default=["base=", "prof1=PROFILE=1", "sync=SERF_RF_SYNC=1", "nolean=SERF_RF_LEAN=0"])
+    ap.add_argument("--variants", nargs="*", default=["base=", "prof1=PROFILE=1", "sync=SERF_RF_SYNC=1"])
     a = ap.parse_args()
     if a.child:
         child(a.ticks, a.profile, a.lib)
