@@ -232,6 +232,62 @@ def ledger_summary(headers, records):
     return out
 
 
+# include/serf_sim_detect.h: detection log (per member that owns a view slot: the episodes in which it was down or accused, judged
+# behind the sampled ticks).  The sixth extension: a version of its own, bound only when the loaded library exports it
+DETECT_SYMBOLS = ("detect_start", "detect_count", "detect_read", "detect_log_count", "detect_log_read", "detect_open", "detect_stop",
+                  "detect_version")
+DETECT_WORDS, DETECT_EPISODE_WORDS, DETECT_MAX_SAMPLES, DETECT_MAX_LOG, DETECT_NEVER = 64, 8, 1 << 20, 1 << 24, 0xFFFFFFFF
+DETECT_DOWN, DETECT_ACCUSED = 1, 2
+DETECT_OPEN, DETECT_DETECTED, DETECT_RETURNED, DETECT_CLEARED, DETECT_STOPPED, DETECT_ABANDONED = range(6)
+DETECT_F_CENSORED, DETECT_F_AFTER_RETURN = 1, 2
+DETECT_OUTCOMES = ("open", "detected", "returned", "cleared", "stopped", "abandoned")
+# a sample's header and one episode as numpy records: the tables of include/serf_sim_detect.h, little-endian, the halves of the
+# packed words under names of their own ("closed" of a header: by outcome 1 .. 5)
+DETECT_HEADER_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("subjects", "<u8"), ("open_down", "<u8"), ("open_accused", "<u8"),
+                                ("closed_now", "<u8"), ("log_written", "<u8"), ("log_lost", "<u8"), ("closed", "<u8", (5,)),
+                                ("false_declared", "<u8"), ("opened_down", "<u8"), ("opened_accused", "<u8"),
+                                ("hist_suspect", "<u8", (16,)), ("hist_all", "<u8", (16,)), ("hist_cleared", "<u8", (16,))])
+DETECT_EPISODE_DTYPE = np.dtype([("subject", "<u4"), ("slot", "<u4"), ("kind", "u1"), ("outcome", "u1"), ("flags", "<u2"), ("zero", "<u4"),
+                                 ("opened", "<u4"), ("closed", "<u4"), ("first_suspect", "<u4"), ("first_failed", "<u4"),
+                                 ("half", "<u4"), ("p99", "<u4"), ("all", "<u4"), ("evaluated", "<u4"), ("peak", "<u8"),
+                                 ("peak_susp", "<u8")])
+assert DETECT_HEADER_DTYPE.itemsize == 8 * DETECT_WORDS and DETECT_EPISODE_DTYPE.itemsize == 8 * DETECT_EPISODE_WORDS
+
+
+def detect_bin(x):
+    """The histogram bin of a latency x (include/serf_sim_detect.h): x == 0 ? 0 : min(15, 1 + floor(log2 x))."""
+    return 0 if x == 0 else min(15, int(x).bit_length())
+
+
+def detect_summary(episodes):
+    """What a detection log says, from its episodes (Sim.detect_log, with or without Sim.detect_open behind them) — a dict
+    "<kind>/<outcome>" -> dict(count, censored, and per latency its median, p99 and the number n of episodes that have it):
+      suspect   first_suspect - opened     failed   first_failed - opened     half, p99, all   likewise (DOWN episodes)
+      length    closed - opened (closed episodes)
+    Latencies are taken over the episodes that are not CENSORED (their `opened` is the first sample, not the stop) and that
+    latched the tick; count covers all, censored says how many of them are."""
+    ep = np.asarray(episodes)
+    out = {}
+    for kind, kname in ((DETECT_DOWN, "down"), (DETECT_ACCUSED, "accused")):
+        for oc, oname in enumerate(DETECT_OUTCOMES):
+            sel = ep[(ep["kind"] == kind) & (ep["outcome"] == oc)] if len(ep) else ep
+            if not len(sel):
+                continue
+            cens = (sel["flags"] & DETECT_F_CENSORED) != 0
+            d = dict(count=int(len(sel)), censored=int(cens.sum()))
+            ok = sel[~cens]
+            lat = [("suspect", "first_suspect"), ("failed", "first_failed"), ("length", "closed")]
+            if kind == DETECT_DOWN:
+                lat += [("half", "half"), ("p99", "p99"), ("all", "all")]
+            for name, field in lat:
+                x = ok[ok[field] != DETECT_NEVER]
+                v = x[field].astype(np.int64) - x["opened"].astype(np.int64)
+                d[name] = dict(n=int(len(v)), median=float(np.median(v)) if len(v) else None,
+                               p99=float(np.percentile(v, 99)) if len(v) else None)
+            out[f"{kname}/{oname}"] = d
+    return out
+
+
 class LedgerEntry(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("key", C.c_uint32), ("val", C.c_uint64)]
 
@@ -381,7 +437,7 @@ class SimLib:
             fn = getattr(self.dll, prefix + name)  # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             self.f[name] = fn
-        # the five extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
+        # the six extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
         # bound whole or not at all
         count = (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)])
         read = (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)])
@@ -425,8 +481,19 @@ class SimLib:
                 "ledger_now": (C.c_int, [H, C.POINTER(LedgerEntry), u32, vp]),
                 "ledger_version": (u32, []),
             }),
+            ("detect", "has_detect", {
+                "detect_start": (C.c_int, [H, u32, u32, u32, u32]),
+                "detect_count": count,
+                "detect_read": read,
+                "detect_log_count": (C.c_int, [H, C.POINTER(u64), C.POINTER(u64)]),
+                "detect_log_read": (C.c_int, [H, u64, u32, vp, u32, C.POINTER(u32)]),
+                "detect_open": (C.c_int, [H, vp, u32, C.POINTER(u32)]),
+                "detect_stop": stop,
+                "detect_version": (u32, []),
+            }),
         ]
-        assert [tuple(sigs) for _, _, sigs in ext] == [TRACK_SYMBOLS, SERIES_SYMBOLS, CENSUS_SYMBOLS, ROLL_SYMBOLS, LEDGER_SYMBOLS]
+        assert [tuple(sigs) for _, _, sigs in ext] == [TRACK_SYMBOLS, SERIES_SYMBOLS, CENSUS_SYMBOLS, ROLL_SYMBOLS, LEDGER_SYMBOLS,
+                                                           DETECT_SYMBOLS]
         self.ext = {}   # group -> exported
         for group, attr, sigs in ext:
             self.ext[group] = all(hasattr(self.dll, prefix + name) for name in sigs)
@@ -474,6 +541,10 @@ class SimLib:
     def ledger_version(self):
         """SIM_LEDGER_VERSION of include/serf_sim_ledger.h, or None when the library has no ledger."""
         return self.f["ledger_version"]() if self.has_ledger else None
+
+    def detect_version(self):
+        """SIM_DETECT_VERSION of include/serf_sim_detect.h, or None when the library has no detection log."""
+        return self.f["detect_version"]() if self.has_detect else None
 
 
 class Sim:
@@ -639,7 +710,7 @@ class Sim:
         self._ck(self.lib.f["convergence_many"](self.h, n, kinds, keys, lts, seen, C.byref(up)), "sim_convergence_many")
         return [int(x) for x in seen[:n]], up.value
 
-    # ---- the extensions: trackers, series, census, roll, ledger (include/serf_sim_<group>.h; the oracle has none of them) ----
+    # ---- the extensions: trackers, series, census, roll, ledger, detection log (include/serf_sim_<group>.h; the oracle has none of them) ----
     def _ext_fn(self, group, name):
         """sim_<group>_<name> of a library that exports the group."""
         if not self.lib.ext[group]:
@@ -820,6 +891,60 @@ class Sim:
         self._ck(fn(self.h, ledger_entries(entries), len(entries), out.ctypes.data), "sim_ledger_now")
         hdr, rec = ledger_split(out[:LEDGER_HEADER_WORDS + len(entries) * LEDGER_ENTRY_WORDS], len(entries))
         return hdr[0], rec[0]
+
+    # ---- detection log (include/serf_sim_detect.h) ----
+    def detect_start(self, first_tick=0, period=1, capacity=1 << 12, log_capacity=1 << 16):
+        """Starts a detection log: behind every tick t >= first_tick with (t - first_tick) % period == 0, until `capacity`
+        samples are held (a first_tick that has passed means "now"), every view slot's subject is judged — down, or running
+        and accused — and the episodes that close are appended to a log of log_capacity records (later ones are counted as
+        lost); a sample is a header of cumulative figures."""
+        self._ck(self._ext_fn("detect", "start")(self.h, first_tick, period, capacity, log_capacity), "sim_detect_start")
+
+    def detect_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        return self._sample_count("detect")
+
+    def detect_read(self, first=0, n=None):
+        """The headers of samples first .. first + n - 1 (n = None: all that were taken from `first` on) as a numpy array of
+        DETECT_HEADER_DTYPE; waits for the handle's stream."""
+        fn = self._ext_fn("detect", "read")
+        if n is None:
+            n = max(0, self._sample_count("detect")[0] - first)
+        out = np.zeros(max(1, n), DETECT_HEADER_DTYPE)
+        got = C.c_uint32()
+        self._ck(fn(self.h, first, n, out.ctypes.data, out.size * DETECT_WORDS, C.byref(got)), "sim_detect_read")
+        return out[:got.value]
+
+    def detect_log_count(self):
+        """(log records written, lost because the log was full); waits for the handle's stream."""
+        w, l = C.c_uint64(), C.c_uint64()
+        self._ck(self._ext_fn("detect", "log_count")(self.h, C.byref(w), C.byref(l)), "sim_detect_log_count")
+        return w.value, l.value
+
+    def detect_log(self, first=0, n=None):
+        """Log records first .. first + n - 1 (n = None: all that were written from `first` on) — the episodes that have
+        closed, in (sample, ascending slot) order — as a numpy array of DETECT_EPISODE_DTYPE; waits for the handle's stream."""
+        fn = self._ext_fn("detect", "log_read")
+        if n is None:
+            n = max(0, self.detect_log_count()[0] - first)
+        out = np.zeros(max(1, n), DETECT_EPISODE_DTYPE)
+        got = C.c_uint32()
+        self._ck(fn(self.h, first, n, out.ctypes.data, len(out), C.byref(got)), "sim_detect_log_read")
+        return out[:got.value]
+
+    def detect_open(self):
+        """The episodes still open (closed = DETECT_NEVER, outcome 0), in ascending slot order, as a numpy array of
+        DETECT_EPISODE_DTYPE; waits for the handle's stream."""
+        fn = self._ext_fn("detect", "open")
+        slots = self.cfg.n_nodes if self.cfg.view_slots == 0 or self.cfg.view_slots >= self.cfg.n_nodes else self.cfg.view_slots
+        out = np.zeros(max(1, slots), DETECT_EPISODE_DTYPE)
+        got = C.c_uint32()
+        self._ck(fn(self.h, out.ctypes.data, len(out), C.byref(got)), "sim_detect_open")
+        return out[:got.value]
+
+    def detect_stop(self):
+        """Ends the detection log and frees its buffers (samples, log and open episodes are gone)."""
+        self._sample_stop("detect")
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

@@ -24,6 +24,7 @@
 #include "../../include/serf_sim_census.h"
 #include "../../include/serf_sim_roll.h"
 #include "../../include/serf_sim_ledger.h"
+#include "../../include/serf_sim_detect.h"
 #include "wire.hpp"
 
 namespace serf {
@@ -318,6 +319,42 @@ class Cluster {
     unpack(words.data(), e.size(), s.header, s.entries);
     return s;
   }
+  // detection log (include/serf_sim_detect.h): behind every period-th tick every view slot's subject is judged — down (when was
+  // the crash first suspected, when did half, 99 % and all of the running nodes know) or running and accused (how far did it get, was
+  // it refuted) — a sample is a header of cumulative figures, the episodes that closed are appended to a log.  HIP library only.
+  void detect_start(uint32_t first_tick = 0, uint32_t period = 1, uint32_t capacity = 1u << 12, uint32_t log_capacity = 1u << 16) {
+    check(sim_detect_start(h_, first_tick, period, capacity, log_capacity), "sim_detect_start");
+  }
+  // (samples taken, dropped with the buffer full); waits for nothing
+  std::pair<uint32_t, uint32_t> detect_count() const { return sample_count(sim_detect_count, "sim_detect_count"); }
+  std::vector<sim_detect_header> detect_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    return sample_read<sim_detect_header>(sim_detect_count, sim_detect_read, "sim_detect", first, n, SIM_DETECT_WORDS,
+                                          [](const uint64_t* w, sim_detect_header& s) { std::memcpy(&s, w, sizeof s); });
+  }
+  // (log records written, lost with the log full); waits for the handle's stream
+  std::pair<uint64_t, uint64_t> detect_log_count() {
+    uint64_t w = 0, l = 0;
+    check(sim_detect_log_count(h_, &w, &l), "sim_detect_log_count");
+    return {w, l};
+  }
+  // the episodes that have closed, in (sample, ascending slot) order (default: all from `first` on)
+  std::vector<sim_detect_episode> detect_log(uint64_t first = 0, uint32_t n = 0xFFFFFFFFu) {
+    if (n == 0xFFFFFFFFu) { const uint64_t w = detect_log_count().first; n = w > first ? (uint32_t)(w - first) : 0; }
+    std::vector<sim_detect_episode> out(n ? n : 1);
+    uint32_t got = 0;
+    check(sim_detect_log_read(h_, first, n, out.data(), (uint32_t)out.size(), &got), "sim_detect_log_read");
+    out.resize(got);
+    return out;
+  }
+  // the episodes still open, in ascending slot order (a slot each: there are no more than nodes)
+  std::vector<sim_detect_episode> detect_open() {
+    std::vector<sim_detect_episode> out(n_);
+    uint32_t got = 0;
+    check(sim_detect_open(h_, out.data(), n_, &got), "sim_detect_open");
+    out.resize(got);
+    return out;
+  }
+  void detect_stop() { check(sim_detect_stop(h_), "sim_detect_stop"); }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;
@@ -336,7 +373,7 @@ class Cluster {
   uint32_t roll_top_ = 1;    // top_k of the running roll: likewise
   uint32_t ledger_n_ = 1;    // entries of the running ledger: likewise
   static_assert(sizeof(LedgerSample::Entry) == 8 * SIM_LEDGER_ENTRY_WORDS, "an entry's record is eight words");
-  // what the four periodic observers share: the count, and "read n samples of `stride` words and unpack each"
+  // what the periodic observers share: the count, and "read n samples of `stride` words and unpack each"
   std::pair<uint32_t, uint32_t> sample_count(int (*count)(const sim_handle*, uint32_t*, uint32_t*), const char* what) const {
     uint32_t t = 0, d = 0;
     check(count(h_, &t, &d), what);

@@ -44,8 +44,14 @@ with the burst and read, summarised (_ffi.ledger_summary: first tick, final reac
 then, copies per node reached) and stopped when the next burst comes: a rumour that outlives the stretch between two bursts shows
 "died_at": null.  The summaries go into the JSON under "ledger".  See profiles/r11_ledger.md.
 
+`--detect PERIOD`: a DETECTION LOG (include/serf_sim_detect.h) behind every PERIOD-th tick: every subject with a view slot is
+judged on the device — nobody is named in advance — and the run's JSON gets, under "detect", _ffi.detect_summary over every
+episode of the run (per kind and outcome the count and the median and 99th percentile of each latency), the last sample's header
+(cumulative counters and the three latency histograms) and the log's counts.  Without the flag nothing about the run changes.
+The run of profiles/r12_config4_detect.json (--tracker --detect 1): see profiles/r12_detect.md.
+
 Needs an MI355X.  Writes one JSON (default profiles/r03_config4_churn5_loss1_swim.json; --tracker: profiles/r07_config4_tracker.json;
---series: profiles/r08_config4_series.json; --census: profiles/r09_config4_census.json; --roll: profiles/r10_config4_roll.json)."""
+--series: profiles/r08_config4_series.json; --census: profiles/r09_config4_census.json; --roll: profiles/r10_config4_roll.json; --detect: profiles/r12_config4_detect.json)."""
 import argparse
 import json
 import os
@@ -157,6 +163,26 @@ def census_json(args, sim):
     return out
 
 
+def detect_json(args, sim):
+    """The run's detection log: _ffi.detect_summary over every episode (closed and still open), the last header, the counts."""
+    from serf_amd import _ffi
+    import numpy as np
+    taken, dropped = sim.detect_count()
+    written, lost = sim.detect_log_count()
+    log, still = sim.detect_log(), sim.detect_open()
+    hdr = sim.detect_read(taken - 1, 1)[0] if taken else None
+    return {"period": args.detect, "samples": int(taken), "dropped": int(dropped), "log_written": int(written), "log_lost": int(lost),
+            "open_at_end": int(len(still)),
+            "what": "include/serf_sim_detect.h: every subject with a view slot, nobody named in advance; a DOWN episode runs from the first "
+                    "sample that sees the subject stopped until every running node holds it Failed or Left (detected), it runs again "
+                    "(returned) or its slot goes to somebody else (abandoned); an ACCUSED episode from the first sample at which a running "
+                    "subject is held Suspect, Dead or Failed by anybody until nobody does (cleared) or it stops; latencies in ticks from "
+                    "`opened`, censored episodes (open at the log's first sample) apart; histogram bin of x: 0 for 0, else min(15, 1 + "
+                    "floor(log2 x))",
+            "summary": _ffi.detect_summary(np.concatenate([log, still])),
+            "last_header": None if hdr is None else {name: (hdr[name].tolist() if hdr[name].ndim else int(hdr[name])) for name in hdr.dtype.names}}
+
+
 def run_tracker(args, sim, lib):
     """The --tracker run: everything the host does happens between two long sim_step calls."""
     import math
@@ -253,6 +279,7 @@ def run_tracker(args, sim, lib):
     census = census_json(args, sim) if args.census else None
     roll = roll_json(args, sim) if args.roll else None
     ledger = ledger.json() if ledger else None
+    detect = detect_json(args, sim) if args.detect else None
 
     def rounds(name):
         return [r[name] - t for t, r in done_ev if r[name] != NEVER]
@@ -284,6 +311,8 @@ def run_tracker(args, sim, lib):
         out["roll"] = roll
     if ledger:
         out["ledger"] = ledger
+    if detect:
+        out["detect"] = detect
     json.dump(out, open(args.out, "w"), indent=None if series or census or roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "sim_step_calls", "crashes", "events", "false_positives", "model_bound_drops", "ops_dropped_no_slot", "wall_s")}), "->", args.out)
     print(json.dumps({"rounds_to_99": out["rounds_to"]["99"], "detection": out["detection"]}))
@@ -324,12 +353,13 @@ def main():
     ap.add_argument("--census", type=int, default=0, metavar="PERIOD", help="count the views of every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_census.h) and put the agreement curves into the JSON")
     ap.add_argument("--roll", type=int, default=0, metavar="PERIOD", help="measure every running node's view against the per-subject references on the device behind every PERIOD-th tick (include/serf_sim_roll.h) and put the curves and the worst observers into the JSON")
     ap.add_argument("--ledger", type=int, default=0, metavar="PERIOD", help="--tracker: follow the first 64 user events with rumour ledgers, sampled behind every PERIOD-th tick (include/serf_sim_ledger.h), and put their summaries into the JSON")
+    ap.add_argument("--detect", type=int, default=0, metavar="PERIOD", help="judge every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_detect.h): the episodes of every crash and every accusation of the run, their summary into the JSON")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.ledger and not args.tracker:
         ap.error("--ledger follows the rumours of a --tracker run")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
+        args.out = os.path.join(ROOT, "profiles", "r12_config4_detect.json" if args.detect else "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
 
     import numpy as np
     from serf_amd import _ffi
@@ -355,6 +385,8 @@ def main():
         sim.census_start(0, args.census, min(_ffi.CENSUS_MAX_SAMPLES, 1 << 16), 1)   # (the headers' curves: one record a sample is the least)
     if args.roll:
         sim.roll_start(0, args.roll, min(_ffi.ROLL_MAX_SAMPLES, 1 << 16), ROLL_TOP, _ffi.ROLL_BY_STALE)
+    if args.detect:
+        sim.detect_start(0, args.detect, min(_ffi.DETECT_MAX_SAMPLES, 1 << 16), 1 << 20)
     if args.tracker:
         return run_tracker(args, sim, lib)
     rng = np.random.default_rng(5)
@@ -410,7 +442,7 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger")},
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect")},
         "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
@@ -439,6 +471,8 @@ def main():
         out["census"] = census_json(args, sim)
     if args.roll:
         out["roll"] = roll_json(args, sim)
+    if args.detect:
+        out["detect"] = detect_json(args, sim)
     json.dump(out, open(args.out, "w"), indent=None if args.series or args.census or args.roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "churn_events", "rounds_to_99", "model_bound_drops", "ops_dropped_no_slot", "failure_detector", "wall_s")}), "->", args.out)
 
