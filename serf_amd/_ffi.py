@@ -288,8 +288,73 @@ def detect_summary(episodes):
     return out
 
 
+# include/serf_sim_spread.h: spread map (per record identity and node: the tick at which the node first had applied it, latched behind
+# the sampled ticks).  The seventh extension: a version of its own, bound only when the loaded library exports it
+SPREAD_SYMBOLS = ("spread_start", "spread_count", "spread_read", "spread_stop", "spread_map", "spread_summary", "spread_unreached",
+                  "spread_late", "spread_version")
+SPREAD_HEADER_WORDS, SPREAD_ENTRY_WORDS, SPREAD_MAX, SPREAD_MAX_SAMPLES = 8, 8, 64, 1 << 20
+SPREAD_BINS, SPREAD_SUMMARY_WORDS, SPREAD_TOP_MAX, SPREAD_NODE_WORDS = 32, 40, 64, 8
+SPREAD_BY_MISSED, SPREAD_BY_LATE = 0, 1
+# a sample's header, one entry's record, one entry's summary and one node's record as numpy records: the tables of
+# include/serf_sim_spread.h ("id" of an entry = key | kind << 32; "id" of a node = the node, "running" its flag)
+SPREAD_HEADER_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("n", "<u8"), ("new", "<u8"), ("started", "<u8"), ("full", "<u8"),
+                                ("reserved", "<u8", (2,))])
+SPREAD_ENTRY_DTYPE = np.dtype([("id", "<u8"), ("val", "<u8"), ("new", "<u8"), ("reached", "<u8"), ("reached_up", "<u8"), ("holds", "<u8"),
+                               ("first", "<u8"), ("last", "<u8")])
+SPREAD_SUMMARY_DTYPE = np.dtype([("id", "<u8"), ("val", "<u8"), ("first", "<u8"), ("last", "<u8"), ("reached", "<u8"), ("reached_up", "<u8"),
+                                 ("unreached_up", "<u8"), ("late_sum", "<u8"), ("bins", "<u8", (SPREAD_BINS,))])
+SPREAD_NODE_DTYPE = np.dtype([("id", "<u4"), ("running", "<u4"), ("got", "<u8"), ("missed", "<u8"), ("late_sum", "<u8"), ("late_max", "<u8"),
+                              ("reserved", "<u8", (3,))])
+assert SPREAD_HEADER_DTYPE.itemsize == 8 * SPREAD_HEADER_WORDS and SPREAD_ENTRY_DTYPE.itemsize == 8 * SPREAD_ENTRY_WORDS
+assert SPREAD_SUMMARY_DTYPE.itemsize == 8 * SPREAD_SUMMARY_WORDS and SPREAD_NODE_DTYPE.itemsize == 8 * SPREAD_NODE_WORDS
+
+
+def spread_split(words, n):
+    """[samples * (8 + 8 * n)] words -> (headers[samples], records[samples][n])."""
+    return sample_split(words, SPREAD_HEADER_DTYPE, SPREAD_ENTRY_DTYPE, n)
+
+
+def spread_percentiles(map_row, qs):
+    """The arrival ticks below which the given shares of the REACHED nodes of one entry lie: for every q of qs (0 < q <= 100)
+    the smallest arrival a such that at least q % of the nodes with a non-zero arrival have one <= a (the nearest-rank
+    percentile: an integer tick that occurs in the row); None for every q when nobody was reached.  map_row: one entry's
+    plane as Sim.spread_map returns it."""
+    a = np.sort(np.asarray(map_row, np.int64)[np.asarray(map_row) != 0])
+    out = []
+    for q in qs:
+        if not 0 < q <= 100:
+            raise ValueError(f"percentile {q} outside (0, 100]")
+        if not len(a):
+            out.append(None)
+            continue
+        rank = -(-int(round(q * 1000)) * len(a) // 100000)          # ceil(q / 100 * len) in integers (q to three decimals)
+        out.append(int(a[max(1, rank) - 1]))
+    return out
+
+
+def spread_rank(nodes, rank_by=SPREAD_BY_MISSED, top_k=None):
+    """The order sim_spread_late lists the RUNNING nodes in, from every node's record (SPREAD_NODE_DTYPE [n_nodes]):
+    SPREAD_BY_MISSED (missed descending, late_sum descending, id ascending), SPREAD_BY_LATE (late_sum descending, missed
+    descending, id ascending).  Returns the node ids, the first top_k of them when given."""
+    nodes = np.asarray(nodes)
+    run = nodes[nodes["running"] != 0]
+    missed, late, ids = run["missed"].astype(np.int64), run["late_sum"].astype(np.int64), run["id"].astype(np.int64)
+    order = np.lexsort((ids, -late, -missed) if rank_by == SPREAD_BY_MISSED else (ids, -missed, -late))
+    return [int(x) for x in ids[order][:top_k]]
+
+
 class LedgerEntry(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("key", C.c_uint32), ("val", C.c_uint64)]
+
+
+class SpreadEntry(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("key", C.c_uint32), ("ltime", C.c_uint64)]
+
+
+def spread_entries(entries):
+    """(kind, key, ltime) triples (or SpreadEntry) -> a ctypes array of SpreadEntry."""
+    es = [e if isinstance(e, SpreadEntry) else SpreadEntry(int(e[0]), int(e[1]), int(e[2])) for e in entries]
+    return (SpreadEntry * max(1, len(es)))(*es)
 
 
 def ledger_entries(entries):
@@ -437,7 +502,7 @@ class SimLib:
             fn = getattr(self.dll, prefix + name)  # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             self.f[name] = fn
-        # the six extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
+        # the seven extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
         # bound whole or not at all
         count = (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)])
         read = (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)])
@@ -491,9 +556,20 @@ class SimLib:
                 "detect_stop": stop,
                 "detect_version": (u32, []),
             }),
+            ("spread", "has_spread", {
+                "spread_start": (C.c_int, [H, C.POINTER(SpreadEntry), u32, u32, u32, u32]),
+                "spread_count": count,
+                "spread_read": read,
+                "spread_stop": stop,
+                "spread_map": (C.c_int, [H, u32, u32, u32, vp]),
+                "spread_summary": (C.c_int, [H, u32, vp]),
+                "spread_unreached": (C.c_int, [H, u32, vp, u32, C.POINTER(u32), C.POINTER(u32)]),
+                "spread_late": (C.c_int, [H, u32, u32, vp, vp]),
+                "spread_version": (u32, []),
+            }),
         ]
         assert [tuple(sigs) for _, _, sigs in ext] == [TRACK_SYMBOLS, SERIES_SYMBOLS, CENSUS_SYMBOLS, ROLL_SYMBOLS, LEDGER_SYMBOLS,
-                                                           DETECT_SYMBOLS]
+                                                           DETECT_SYMBOLS, SPREAD_SYMBOLS]
         self.ext = {}   # group -> exported
         for group, attr, sigs in ext:
             self.ext[group] = all(hasattr(self.dll, prefix + name) for name in sigs)
@@ -545,6 +621,10 @@ class SimLib:
     def detect_version(self):
         """SIM_DETECT_VERSION of include/serf_sim_detect.h, or None when the library has no detection log."""
         return self.f["detect_version"]() if self.has_detect else None
+
+    def spread_version(self):
+        """SIM_SPREAD_VERSION of include/serf_sim_spread.h, or None when the library has no spread map."""
+        return self.f["spread_version"]() if self.has_spread else None
 
 
 class Sim:
@@ -710,7 +790,7 @@ class Sim:
         self._ck(self.lib.f["convergence_many"](self.h, n, kinds, keys, lts, seen, C.byref(up)), "sim_convergence_many")
         return [int(x) for x in seen[:n]], up.value
 
-    # ---- the extensions: trackers, series, census, roll, ledger, detection log (include/serf_sim_<group>.h; the oracle has none of them) ----
+    # ---- the extensions: trackers, series, census, roll, ledger, detection log, spread map (include/serf_sim_<group>.h; the oracle has none of them) ----
     def _ext_fn(self, group, name):
         """sim_<group>_<name> of a library that exports the group."""
         if not self.lib.ext[group]:
@@ -945,6 +1025,67 @@ class Sim:
     def detect_stop(self):
         """Ends the detection log and frees its buffers (samples, log and open episodes are gone)."""
         self._sample_stop("detect")
+
+    # ---- spread map (include/serf_sim_spread.h) ----
+    def spread_start(self, entries=(), first_tick=0, period=1, capacity=1 << 12):
+        """Starts a spread map of `entries` ((kind, key, ltime) triples of kinds K_JOIN .. K_QUERY, 64 at most): behind every
+        tick t >= first_tick with (t - first_tick) % period == 0, until `capacity` samples are held (a first_tick that has
+        passed means "now"), every running node that has applied an entry's rumour and has no arrival for it yet gets
+        arrival = t + 1; a sample is a header and per entry what it latched and where the entry stands."""
+        fn = self._ext_fn("spread", "start")
+        self._ck(fn(self.h, spread_entries(entries), len(entries), first_tick, period, capacity), "sim_spread_start")
+        self._spread_n = len(entries)
+
+    def spread_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        return self._sample_count("spread")
+
+    def spread_read(self, first=0, n=None):
+        """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as (headers, records): numpy
+        arrays of SPREAD_HEADER_DTYPE [n] and SPREAD_ENTRY_DTYPE [n][entries]; waits for the handle's stream."""
+        return self._sample_read("spread", first, n, SPREAD_HEADER_DTYPE, SPREAD_ENTRY_DTYPE, getattr(self, "_spread_n", 1))
+
+    def spread_stop(self):
+        """Ends the spread map and frees the map and the samples."""
+        self._sample_stop("spread")
+
+    def spread_map(self, entry, first_node=0, count=None):
+        """arrival[entry][first_node .. first_node + count - 1] (count = None: up to the last node) as a numpy array of
+        uint32, 0 = not yet; waits for the handle's stream."""
+        if count is None:
+            count = max(0, self.cfg.n_nodes - first_node)
+        out = np.zeros(max(1, count), np.uint32)
+        self._ck(self._ext_fn("spread", "map")(self.h, entry, first_node, count, out.ctypes.data), "sim_spread_map")
+        return out[:count]
+
+    def spread_summary(self, bin_width=1):
+        """Every entry's summary as a numpy array of SPREAD_SUMMARY_DTYPE [entries]: first and last arrival, the reached,
+        the running nodes not reached, the sum and the histogram of arrival - first in bins of bin_width ticks; waits for
+        the handle's stream."""
+        out = np.zeros(max(1, getattr(self, "_spread_n", 1)), SPREAD_SUMMARY_DTYPE)
+        self._ck(self._ext_fn("spread", "summary")(self.h, bin_width, out.ctypes.data), "sim_spread_summary")
+        return out[:getattr(self, "_spread_n", 1)]
+
+    def spread_unreached(self, entry, cap=None):
+        """(ids, total): the running nodes without an arrival for `entry` in ascending id — the first `cap` of them
+        (cap = None: all) — and the number of all of them; waits for the handle's stream."""
+        if cap is None:
+            cap = self.cfg.n_nodes
+        ids = np.zeros(max(1, cap), np.uint32)
+        got, total = C.c_uint32(), C.c_uint32()
+        self._ck(self._ext_fn("spread", "unreached")(self.h, entry, ids.ctypes.data if cap else None, cap, C.byref(got), C.byref(total)),
+                 "sim_spread_unreached")
+        return ids[:got.value], total.value
+
+    def spread_late(self, top_k=8, rank_by=SPREAD_BY_MISSED, nodes=False):
+        """The top_k worst running nodes by rank_by (SPREAD_BY_MISSED / SPREAD_BY_LATE) as a numpy array of SPREAD_NODE_DTYPE
+        [top_k] (records beyond the running nodes are zero), and with nodes=True (top, every node's record [n_nodes]); waits
+        for the handle's stream."""
+        top = np.zeros(max(1, top_k), SPREAD_NODE_DTYPE)
+        every = np.zeros(self.cfg.n_nodes, SPREAD_NODE_DTYPE) if nodes else None
+        self._ck(self._ext_fn("spread", "late")(self.h, top_k, rank_by, top.ctypes.data, every.ctypes.data if nodes else None),
+                 "sim_spread_late")
+        return (top[:top_k], every) if nodes else top[:top_k]
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

@@ -24,6 +24,7 @@
 #include "../../include/serf_sim_census.h"
 #include "../../include/serf_sim_roll.h"
 #include "../../include/serf_sim_ledger.h"
+#include "../../include/serf_sim_spread.h"
 #include "../../include/serf_sim_detect.h"
 #include "wire.hpp"
 
@@ -355,6 +356,63 @@ class Cluster {
     return out;
   }
   void detect_stop() { check(sim_detect_stop(h_), "sim_detect_stop"); }
+  // spread map (include/serf_sim_spread.h): behind every period-th tick every running node that has applied one of up to 64
+  // rumours (kind 1-4, key, ltime) and has no arrival for it yet gets arrival = tick + 1 — which nodes got a rumour late or never,
+  // and when each node got it.  A sample says what it latched and where each entry stands; the map is read by entry (spread_map),
+  // summed up (spread_summary), by its gaps (spread_unreached) or by node (spread_late).  HIP library only.
+  struct SpreadSample {
+    uint64_t header[SIM_SPREAD_HEADER_WORDS];  // now, running, n, latched now, entries started, entries everybody running has, 0, 0
+    struct Entry { uint64_t id, val, latched, reached, reached_up, holds, first, last; };  // id = key | kind << 32
+    std::vector<Entry> entries;                // in the order they were given
+  };
+  struct SpreadSummary { uint64_t id, val, first, last, reached, reached_up, unreached_up, late_sum, bins[SIM_SPREAD_BINS]; };
+  struct SpreadLate {
+    std::vector<sim_spread_node> top;    // the worst running nodes, worst first; records beyond the running nodes are zero
+    std::vector<sim_spread_node> nodes;  // every node's record, when asked for
+  };
+  void spread_start(const std::vector<sim_spread_entry>& e, uint32_t first_tick = 0, uint32_t period = 1, uint32_t capacity = 1u << 12) {
+    check(sim_spread_start(h_, e.data(), (uint32_t)e.size(), first_tick, period, capacity), "sim_spread_start");
+    spread_n_ = (uint32_t)e.size();
+  }
+  // (samples taken, dropped with the buffer full); waits for nothing
+  std::pair<uint32_t, uint32_t> spread_count() const { return sample_count(sim_spread_count, "sim_spread_count"); }
+  std::vector<SpreadSample> spread_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    const uint32_t ne = spread_n_;
+    return sample_read<SpreadSample>(sim_spread_count, sim_spread_read, "sim_spread", first, n, SIM_SPREAD_HEADER_WORDS + (size_t)ne * SIM_SPREAD_ENTRY_WORDS,
+                                     [ne](const uint64_t* w, SpreadSample& s) { unpack(w, ne, s.header, s.entries); });
+  }
+  void spread_stop() { check(sim_spread_stop(h_), "sim_spread_stop"); }
+  // arrival[entry][first_node ..]: 0 = not yet (default: up to the last node)
+  std::vector<uint32_t> spread_map(uint32_t entry, uint32_t first_node = 0, uint32_t count = 0xFFFFFFFFu) {
+    if (count == 0xFFFFFFFFu) count = n_ > first_node ? n_ - first_node : 0;
+    std::vector<uint32_t> out(count ? count : 1);
+    check(sim_spread_map(h_, entry, first_node, count, out.data()), "sim_spread_map");
+    out.resize(count);
+    return out;
+  }
+  std::vector<SpreadSummary> spread_summary(uint32_t bin_width = 1) {
+    std::vector<SpreadSummary> out(spread_n_ ? spread_n_ : 1);
+    check(sim_spread_summary(h_, bin_width, reinterpret_cast<uint64_t*>(out.data())), "sim_spread_summary");
+    out.resize(spread_n_);
+    return out;
+  }
+  // (the running nodes without an arrival for `entry` in ascending id, the first `cap` of them; the number of all of them)
+  std::pair<std::vector<uint32_t>, uint32_t> spread_unreached(uint32_t entry, uint32_t cap = 0xFFFFFFFFu) {
+    if (cap > n_) cap = n_;
+    std::vector<uint32_t> ids(cap ? cap : 1);
+    uint32_t got = 0, total = 0;
+    check(sim_spread_unreached(h_, entry, ids.data(), cap, &got, &total), "sim_spread_unreached");
+    ids.resize(got);
+    return {ids, total};
+  }
+  SpreadLate spread_late(uint32_t top_k = 8, uint32_t rank_by = SIM_SPREAD_BY_MISSED, bool nodes = false) {
+    SpreadLate s;
+    s.top.resize(top_k ? top_k : 1);
+    if (nodes) s.nodes.resize(n_);
+    check(sim_spread_late(h_, top_k, rank_by, s.top.data(), nodes ? s.nodes.data() : nullptr), "sim_spread_late");
+    s.top.resize(top_k);
+    return s;
+  }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;
@@ -372,6 +430,9 @@ class Cluster {
   uint32_t census_max_ = 1;  // max_subjects of the running census: the stride of its samples
   uint32_t roll_top_ = 1;    // top_k of the running roll: likewise
   uint32_t ledger_n_ = 1;    // entries of the running ledger: likewise
+  uint32_t spread_n_ = 1;    // entries of the running spread map: likewise
+  static_assert(sizeof(SpreadSample::Entry) == 8 * SIM_SPREAD_ENTRY_WORDS && sizeof(SpreadSummary) == 8 * SIM_SPREAD_SUMMARY_WORDS,
+                "an entry's record is eight words, its summary forty");
   static_assert(sizeof(LedgerSample::Entry) == 8 * SIM_LEDGER_ENTRY_WORDS, "an entry's record is eight words");
   // what the periodic observers share: the count, and "read n samples of `stride` words and unpack each"
   std::pair<uint32_t, uint32_t> sample_count(int (*count)(const sim_handle*, uint32_t*, uint32_t*), const char* what) const {

@@ -44,6 +44,10 @@ with the burst and read, summarised (_ffi.ledger_summary: first tick, final reac
 then, copies per node reached) and stopped when the next burst comes: a rumour that outlives the stretch between two bursts shows
 "died_at": null.  The summaries go into the JSON under "ledger".  See profiles/r11_ledger.md.
 
+`--spread PERIOD` (with --tracker): a SPREAD MAP (include/serf_sim_spread.h) of the first 64 user events the trackers follow, a map
+per burst as for --ledger: when each node first had each event.  Per event the JSON gets, under "spread", the first and last arrival,
+the reached and the running nodes never reached, the histogram of arrival - first and the arrival percentiles (_ffi.spread_percentiles).
+
 `--detect PERIOD`: a DETECTION LOG (include/serf_sim_detect.h) behind every PERIOD-th tick: every subject with a view slot is
 judged on the device — nobody is named in advance — and the run's JSON gets, under "detect", _ffi.detect_summary over every
 episode of the run (per kind and outcome the count and the median and 99th percentile of each latency), the last sample's header
@@ -142,6 +146,49 @@ class LedgerRun:
                         "of the last sample with a copy queued or in flight when a later sample exists; copies_per_node = copies / reach"}
 
 
+class SpreadRun:
+    """--spread: one spread map per burst of user events until SPREAD_MAX rumours have been followed."""
+
+    def __init__(self, args, sim):
+        from serf_amd import _ffi
+        self.ffi, self.args, self.sim = _ffi, args, sim
+        self.followed, self.open_at, self.done, self.dropped = 0, None, [], 0
+
+    def close(self):
+        if self.open_at is None:
+            return
+        taken, dropped = self.sim.spread_count()
+        self.dropped += dropped
+        for i, s in enumerate(self.sim.spread_summary(1)):
+            bins = [int(x) for x in s["bins"]]
+            while bins and not bins[-1]:
+                bins.pop()
+            pct = self.ffi.spread_percentiles(self.sim.spread_map(i), (50, 90, 99, 100))
+            self.done.append({"injected_at": self.open_at, "samples": int(taken), "key": int(s["id"] & 0xFFFFFFFF), "ltime": int(s["val"]),
+                              "first": int(s["first"]), "last": int(s["last"]), "reached": int(s["reached"]), "reached_up": int(s["reached_up"]),
+                              "unreached_up": int(s["unreached_up"]), "mean_delay": float(s["late_sum"]) / int(s["reached"]) if s["reached"] else None,
+                              "arrival_percentiles": dict(zip(("50", "90", "99", "100"), pct)), "histogram": bins})
+        self.sim.spread_stop()
+        self.open_at = None
+
+    def burst(self, t, rumours):
+        """rumours: (kind, key, ltime) of the events about to be injected at tick t."""
+        if self.followed >= self.ffi.SPREAD_MAX:
+            return
+        self.close()
+        take = rumours[:self.ffi.SPREAD_MAX - self.followed]
+        self.sim.spread_start(take, 0, self.args.spread, 1 << 12)
+        self.open_at, self.followed = int(t), self.followed + len(take)
+
+    def json(self):
+        self.close()
+        return {"period": self.args.spread, "rumours": self.done, "dropped": self.dropped,
+                "what": "include/serf_sim_spread.h: per followed user event (the first 64, a map per burst, ended by the next burst): first / "
+                        "last = the smallest / largest arrival (sim_tick); reached = nodes with an arrival; unreached_up = running nodes "
+                        "without one when the map ended; histogram = reached nodes by arrival - first, a tick a bin, the 32nd taking "
+                        "everything beyond; arrival_percentiles = the tick by which that share of the reached nodes had it"}
+
+
 def census_json(args, sim):
     """The headers of the run's census, one list per field of _ffi.CENSUS_HEADER_DTYPE, and the records of the state at the end."""
     taken, dropped = sim.census_count()
@@ -221,6 +268,7 @@ def run_tracker(args, sim, lib):
     live_ev, done_ev, done_cr = [], [], []   # (id, inject tick) / (inject tick, result) / (crash tick, suspect+, failed)
     ci = 0
     ledger = LedgerRun(args, sim) if args.ledger else None
+    spread = SpreadRun(args, sim) if args.spread else None
     t0 = time.perf_counter()
     stretches = 0
 
@@ -266,6 +314,8 @@ def run_tracker(args, sim, lib):
             live_ev += [(i, t) for i in sim.track_add(specs)]
             if ledger:
                 ledger.burst(t, [(sp.a, sp.b, sp.ltime) for sp in specs])
+            if spread:
+                spread.burst(t, [(sp.a, sp.b, sp.ltime) for sp in specs])
             for node, key in keys:
                 sim.user_event(node, key, 64)
         sim.step(min(every, total - t))     # ONE call per stretch; nothing is read back inside it
@@ -279,6 +329,7 @@ def run_tracker(args, sim, lib):
     census = census_json(args, sim) if args.census else None
     roll = roll_json(args, sim) if args.roll else None
     ledger = ledger.json() if ledger else None
+    spread = spread.json() if spread else None
     detect = detect_json(args, sim) if args.detect else None
 
     def rounds(name):
@@ -311,6 +362,8 @@ def run_tracker(args, sim, lib):
         out["roll"] = roll
     if ledger:
         out["ledger"] = ledger
+    if spread:
+        out["spread"] = spread
     if detect:
         out["detect"] = detect
     json.dump(out, open(args.out, "w"), indent=None if series or census or roll else 1)
@@ -353,13 +406,16 @@ def main():
     ap.add_argument("--census", type=int, default=0, metavar="PERIOD", help="count the views of every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_census.h) and put the agreement curves into the JSON")
     ap.add_argument("--roll", type=int, default=0, metavar="PERIOD", help="measure every running node's view against the per-subject references on the device behind every PERIOD-th tick (include/serf_sim_roll.h) and put the curves and the worst observers into the JSON")
     ap.add_argument("--ledger", type=int, default=0, metavar="PERIOD", help="--tracker: follow the first 64 user events with rumour ledgers, sampled behind every PERIOD-th tick (include/serf_sim_ledger.h), and put their summaries into the JSON")
+    ap.add_argument("--spread", type=int, default=0, metavar="PERIOD", help="--tracker: follow the first 64 user events with spread maps, latched behind every PERIOD-th tick (include/serf_sim_spread.h), and put their arrival histograms and unreached counts into the JSON")
     ap.add_argument("--detect", type=int, default=0, metavar="PERIOD", help="judge every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_detect.h): the episodes of every crash and every accusation of the run, their summary into the JSON")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.ledger and not args.tracker:
         ap.error("--ledger follows the rumours of a --tracker run")
+    if args.spread and not args.tracker:
+        ap.error("--spread follows the rumours of a --tracker run")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r12_config4_detect.json" if args.detect else "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
+        args.out = os.path.join(ROOT, "profiles", "r12_config4_detect.json" if args.detect else "r13_config4_spread.json" if args.spread else "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
 
     import numpy as np
     from serf_amd import _ffi
@@ -442,7 +498,7 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect")},
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect", "spread")},
         "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
