@@ -343,6 +343,51 @@ def spread_rank(nodes, rank_by=SPREAD_BY_MISSED, top_k=None):
     return [int(x) for x in ids[order][:top_k]]
 
 
+# include/serf_sim_traffic.h: traffic meter (per node the gossip packets, records and 16-byte units it sent and had addressed to it,
+# accumulated behind the sampled ticks).  The eighth extension: a version of its own, bound only when the loaded library exports it
+TRAFFIC_SYMBOLS = ("traffic_start", "traffic_count", "traffic_read", "traffic_stop", "traffic_nodes", "traffic_top", "traffic_summary",
+                   "traffic_version")
+TRAFFIC_WORDS, TRAFFIC_MAX_SAMPLES, TRAFFIC_COLUMNS, TRAFFIC_TOP_MAX = 64, 1 << 20, 8, 64
+TRAFFIC_DEG_BINS, TRAFFIC_REC_BINS, TRAFFIC_BINS, TRAFFIC_SUMMARY_WORDS = 32, 16, 32, 40
+TRAFFIC_COLUMN_NAMES = ("tx_packets", "tx_records", "tx_units", "rx_packets", "rx_records", "rx_units", "rx_peak", "rx_down")
+TRAFFIC_UNIT_BYTES = 16
+# a sample, a node's record, a ranked node and a column's summary as numpy records: the tables of include/serf_sim_traffic.h
+TRAFFIC_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("packets", "<u8"), ("records", "<u8"), ("units", "<u8"), ("senders", "<u8"),
+                          ("addressed", "<u8"), ("to_down", "<u8"), ("max_packets", "<u8"), ("max_packets_id", "<u8"), ("max_units", "<u8"),
+                          ("max_units_id", "<u8"), ("packet_records_max", "<u8"), ("packet_units_max", "<u8"), ("samples", "<u8"),
+                          ("reserved", "<u8"), ("degree_bins", "<u8", (TRAFFIC_DEG_BINS,)), ("record_bins", "<u8", (TRAFFIC_REC_BINS,))])
+TRAFFIC_NODE_DTYPE = np.dtype([(name, "<u4") for name in TRAFFIC_COLUMN_NAMES])
+TRAFFIC_RANK_DTYPE = np.dtype([("id", "<u4"), ("running", "<u4"), ("node", TRAFFIC_NODE_DTYPE)])
+TRAFFIC_SUMMARY_DTYPE = np.dtype([("column", "<u8"), ("bin_width", "<u8"), ("sum", "<u8"), ("max", "<u8"), ("max_id", "<u8"), ("min", "<u8"),
+                                  ("nonzero", "<u8"), ("samples", "<u8"), ("bins", "<u8", (TRAFFIC_BINS,))])
+assert TRAFFIC_DTYPE.itemsize == 8 * TRAFFIC_WORDS and TRAFFIC_NODE_DTYPE.itemsize == 32 and TRAFFIC_RANK_DTYPE.itemsize == 40
+assert TRAFFIC_SUMMARY_DTYPE.itemsize == 8 * TRAFFIC_SUMMARY_WORDS
+
+
+class TrafficNode(C.Structure):
+    _fields_ = [("col", C.c_uint32 * TRAFFIC_COLUMNS)]
+
+
+class TrafficRank(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("running", C.c_uint32), ("node", TrafficNode)]
+
+
+def traffic_rates(nodes, samples, interval_ms=200):
+    """Bytes per second every node sent and had addressed to it, from the map (TRAFFIC_NODE_DTYPE [n_nodes], as Sim.traffic_nodes
+    returns it) accumulated over `samples` samples, each standing for one gossip interval of interval_ms: a dict with the two
+    arrays "tx" and "rx" (float64 [n_nodes]) and, under "tx_stats" / "rx_stats", their median, 99th percentile and max.  With a
+    sampling period above 1 the rates are those of the sampled intervals."""
+    nodes = np.asarray(nodes)
+    seconds = samples * interval_ms / 1000.0
+    out = {}
+    for side in ("tx", "rx"):
+        rate = nodes[side + "_units"].astype(np.float64) * TRAFFIC_UNIT_BYTES / seconds if seconds > 0 else np.zeros(len(nodes))
+        out[side] = rate
+        out[side + "_stats"] = ({"median": float(np.median(rate)), "p99": float(np.percentile(rate, 99)), "max": float(rate.max())}
+                                if len(rate) else {"median": 0.0, "p99": 0.0, "max": 0.0})
+    return out
+
+
 class LedgerEntry(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("key", C.c_uint32), ("val", C.c_uint64)]
 
@@ -567,9 +612,19 @@ class SimLib:
                 "spread_late": (C.c_int, [H, u32, u32, vp, vp]),
                 "spread_version": (u32, []),
             }),
+            ("traffic", "has_traffic", {
+                "traffic_start": (C.c_int, [H, u32, u32, u32]),
+                "traffic_count": count,
+                "traffic_read": read,
+                "traffic_stop": stop,
+                "traffic_nodes": (C.c_int, [H, u32, u32, vp]),
+                "traffic_top": (C.c_int, [H, u32, u32, vp]),
+                "traffic_summary": (C.c_int, [H, u32, u32, vp]),
+                "traffic_version": (u32, []),
+            }),
         ]
         assert [tuple(sigs) for _, _, sigs in ext] == [TRACK_SYMBOLS, SERIES_SYMBOLS, CENSUS_SYMBOLS, ROLL_SYMBOLS, LEDGER_SYMBOLS,
-                                                           DETECT_SYMBOLS, SPREAD_SYMBOLS]
+                                                           DETECT_SYMBOLS, SPREAD_SYMBOLS, TRAFFIC_SYMBOLS]
         self.ext = {}   # group -> exported
         for group, attr, sigs in ext:
             self.ext[group] = all(hasattr(self.dll, prefix + name) for name in sigs)
@@ -625,6 +680,10 @@ class SimLib:
     def spread_version(self):
         """SIM_SPREAD_VERSION of include/serf_sim_spread.h, or None when the library has no spread map."""
         return self.f["spread_version"]() if self.has_spread else None
+
+    def traffic_version(self):
+        """SIM_TRAFFIC_VERSION of include/serf_sim_traffic.h, or None when the library has no traffic meter."""
+        return self.f["traffic_version"]() if self.has_traffic else None
 
 
 class Sim:
@@ -1086,6 +1145,57 @@ class Sim:
         self._ck(self._ext_fn("spread", "late")(self.h, top_k, rank_by, top.ctypes.data, every.ctypes.data if nodes else None),
                  "sim_spread_late")
         return (top[:top_k], every) if nodes else top[:top_k]
+
+    # ---- traffic meter (include/serf_sim_traffic.h) ----
+    def traffic_start(self, first_tick=0, period=1, capacity=1 << 12):
+        """Starts the traffic meter: behind every tick t >= first_tick with (t - first_tick) % period == 0, until `capacity`
+        samples are held (a first_tick that has passed means "now"), the gossip packets in flight are counted per sender and
+        per target into the map (eight uint32 a node, from zero) and summed up in a sample of 64 words."""
+        self._ck(self._ext_fn("traffic", "start")(self.h, first_tick, period, capacity), "sim_traffic_start")
+
+    def traffic_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        return self._sample_count("traffic")
+
+    def traffic_read(self, first=0, n=None):
+        """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as a numpy array of TRAFFIC_DTYPE;
+        waits for the handle's stream."""
+        fn = self._ext_fn("traffic", "read")
+        if n is None:
+            n = max(0, self._sample_count("traffic")[0] - first)
+        out = np.zeros(max(1, n) * TRAFFIC_WORDS, np.uint64)
+        got = C.c_uint32()
+        self._ck(fn(self.h, first, n, out.ctypes.data, out.size, C.byref(got)), "sim_traffic_read")
+        return out[:got.value * TRAFFIC_WORDS].view(TRAFFIC_DTYPE)
+
+    def traffic_stop(self):
+        """Ends the meter and frees the map and the samples."""
+        self._sample_stop("traffic")
+
+    def traffic_nodes(self, first_node=0, count=None):
+        """The map's records of nodes first_node .. first_node + count - 1 (count = None: up to the last node) as a numpy array
+        of TRAFFIC_NODE_DTYPE; waits for the handle's stream."""
+        if count is None:
+            count = max(0, self.cfg.n_nodes - first_node)
+        out = np.zeros(max(1, count), TRAFFIC_NODE_DTYPE)
+        self._ck(self._ext_fn("traffic", "nodes")(self.h, first_node, count, out.ctypes.data), "sim_traffic_nodes")
+        return out[:count]
+
+    def traffic_top(self, top_k=10, column=5):
+        """ALL nodes ranked by a column of the map (0 .. 7, TRAFFIC_COLUMN_NAMES; default rx_units) descending, ties by ascending
+        id: the first top_k as a numpy array of TRAFFIC_RANK_DTYPE (records beyond n_nodes: id 0xFFFFFFFF and zeros); waits for
+        the handle's stream."""
+        top = np.zeros(max(1, top_k), TRAFFIC_RANK_DTYPE)
+        self._ck(self._ext_fn("traffic", "top")(self.h, top_k, column, top.ctypes.data), "sim_traffic_top")
+        return top[:top_k]
+
+    def traffic_summary(self, column=5, bin_width=1):
+        """One column of the map over all nodes as a numpy record of TRAFFIC_SUMMARY_DTYPE: sum, max and the smallest id that has
+        it, min, the nodes with a non-zero value, the samples accumulated and the histogram in bins of bin_width; waits for the
+        handle's stream."""
+        out = np.zeros(1, TRAFFIC_SUMMARY_DTYPE)
+        self._ck(self._ext_fn("traffic", "summary")(self.h, column, bin_width, out.ctypes.data), "sim_traffic_summary")
+        return out[0]
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

@@ -86,3 +86,4 @@ extern "C" {
 #include "serf_sim_ledger.inc"  // include/serf_sim_ledger.h: likewise
 #include "serf_sim_detect.inc"  // include/serf_sim_detect.h: likewise
 #include "serf_sim_spread.inc"  // include/serf_sim_spread.h: likewise
+#include "serf_sim_traffic.inc"  // include/serf_sim_traffic.h: likewise

@@ -25,6 +25,7 @@
 #include "../../include/serf_sim_roll.h"
 #include "../../include/serf_sim_ledger.h"
 #include "../../include/serf_sim_spread.h"
+#include "../../include/serf_sim_traffic.h"
 #include "../../include/serf_sim_detect.h"
 #include "wire.hpp"
 
@@ -413,6 +414,42 @@ class Cluster {
     s.top.resize(top_k);
     return s;
   }
+  // traffic meter (include/serf_sim_traffic.h): behind every period-th tick the gossip packets in flight are counted per sender and per
+  // target — packets, records, 16-byte units — into a map of eight uint32_t a node, and a sample says how the load was spread: the
+  // in-degree histogram, the most addressed node, what went to stopped processes.  The map is read by node (traffic_nodes), ranked
+  // (traffic_top) or summed up by column (traffic_summary).  HIP library only.
+  struct TrafficSample { uint64_t w[SIM_TRAFFIC_WORDS]; };   // the table of include/serf_sim_traffic.h
+  struct TrafficSummary { uint64_t column, bin_width, sum, max, max_id, min, nonzero, samples, bins[SIM_TRAFFIC_BINS]; };
+  void traffic_start(uint32_t first_tick = 0, uint32_t period = 1, uint32_t capacity = 1u << 12) {
+    check(sim_traffic_start(h_, first_tick, period, capacity), "sim_traffic_start");
+  }
+  // (samples taken, dropped with the buffer full); waits for nothing
+  std::pair<uint32_t, uint32_t> traffic_count() const { return sample_count(sim_traffic_count, "sim_traffic_count"); }
+  std::vector<TrafficSample> traffic_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    return sample_read<TrafficSample>(sim_traffic_count, sim_traffic_read, "sim_traffic", first, n, SIM_TRAFFIC_WORDS,
+                                      [](const uint64_t* w, TrafficSample& s) { std::memcpy(&s, w, sizeof s); });
+  }
+  void traffic_stop() { check(sim_traffic_stop(h_), "sim_traffic_stop"); }
+  // the map's records of nodes first_node .. (default: up to the last node)
+  std::vector<sim_traffic_node> traffic_nodes(uint32_t first_node = 0, uint32_t count = 0xFFFFFFFFu) {
+    if (count == 0xFFFFFFFFu) count = n_ > first_node ? n_ - first_node : 0;
+    std::vector<sim_traffic_node> out(count ? count : 1);
+    check(sim_traffic_nodes(h_, first_node, count, out.data()), "sim_traffic_nodes");
+    out.resize(count);
+    return out;
+  }
+  // ALL nodes ranked by a column (SIM_TRAFFIC_TX_PACKETS .. SIM_TRAFFIC_RX_DOWN) descending, ties by ascending id: the first top_k
+  std::vector<sim_traffic_rank> traffic_top(uint32_t top_k = 10, uint32_t column = SIM_TRAFFIC_RX_UNITS) {
+    std::vector<sim_traffic_rank> out(top_k ? top_k : 1);
+    check(sim_traffic_top(h_, top_k, column, out.data()), "sim_traffic_top");
+    out.resize(top_k);
+    return out;
+  }
+  TrafficSummary traffic_summary(uint32_t column = SIM_TRAFFIC_RX_UNITS, uint32_t bin_width = 1) {
+    TrafficSummary s;
+    check(sim_traffic_summary(h_, column, bin_width, reinterpret_cast<uint64_t*>(&s)), "sim_traffic_summary");
+    return s;
+  }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;
@@ -434,6 +471,8 @@ class Cluster {
   static_assert(sizeof(SpreadSample::Entry) == 8 * SIM_SPREAD_ENTRY_WORDS && sizeof(SpreadSummary) == 8 * SIM_SPREAD_SUMMARY_WORDS,
                 "an entry's record is eight words, its summary forty");
   static_assert(sizeof(LedgerSample::Entry) == 8 * SIM_LEDGER_ENTRY_WORDS, "an entry's record is eight words");
+  static_assert(sizeof(TrafficSample) == 8 * SIM_TRAFFIC_WORDS && sizeof(TrafficSummary) == 8 * SIM_TRAFFIC_SUMMARY_WORDS,
+                "a traffic sample is sixty-four words, a column's summary forty");
   // what the periodic observers share: the count, and "read n samples of `stride` words and unpack each"
   std::pair<uint32_t, uint32_t> sample_count(int (*count)(const sim_handle*, uint32_t*, uint32_t*), const char* what) const {
     uint32_t t = 0, d = 0;

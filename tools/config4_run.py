@@ -54,6 +54,12 @@ episode of the run (per kind and outcome the count and the median and 99th perce
 (cumulative counters and the three latency histograms) and the log's counts.  Without the flag nothing about the run changes.
 The run of profiles/r12_config4_detect.json (--tracker --detect 1): see profiles/r12_detect.md.
 
+`--traffic PERIOD`: a TRAFFIC METER (include/serf_sim_traffic.h) behind every PERIOD-th tick: per node the gossip packets, records and
+wire bytes it sent and had addressed to it.  The run's JSON gets, under "traffic", the bytes per second sent and addressed per node
+(median, 99th percentile, max and the 99th-percentile-to-median ratio; _ffi.traffic_rates), the ten nodes the most bytes were addressed
+to, the share of the packets that were addressed to stopped processes, the summed in-degree histogram of the samples and the
+summary of rx_units.  Without the flag nothing about the run changes; it goes with either kind of run.  See profiles/r14_traffic.md.
+
 Needs an MI355X.  Writes one JSON (default profiles/r03_config4_churn5_loss1_swim.json; --tracker: profiles/r07_config4_tracker.json;
 --series: profiles/r08_config4_series.json; --census: profiles/r09_config4_census.json; --roll: profiles/r10_config4_roll.json; --detect: profiles/r12_config4_detect.json)."""
 import argparse
@@ -230,6 +236,33 @@ def detect_json(args, sim):
             "last_header": None if hdr is None else {name: (hdr[name].tolist() if hdr[name].ndim else int(hdr[name])) for name in hdr.dtype.names}}
 
 
+def traffic_json(args, sim):
+    """The run's traffic meter: per-node byte rates, the hottest receivers, what went to stopped processes, the in-degree histogram."""
+    from serf_amd import _ffi
+    taken, dropped = sim.traffic_count()
+    s = sim.traffic_read()
+    nodes = sim.traffic_nodes()
+    rates = _ffi.traffic_rates(nodes, int(taken))
+    for side in ("tx_stats", "rx_stats"):
+        st = rates[side]
+        st["p99_over_median"] = st["p99"] / st["median"] if st["median"] else None
+    packets, to_down = int(s["packets"].sum()), int(s["to_down"].sum())
+    summ = sim.traffic_summary(5, 64)
+    return {"period": args.traffic, "samples": int(taken), "dropped": int(dropped),
+            "what": "include/serf_sim_traffic.h: a packet = one (sender, fan-out slot) in flight behind a sampled tick with at least one record; "
+                    "bytes = 16-byte units of its records; addressed = to the slot's target, running or not; rates: a sample stands for one "
+                    "gossip interval of 200 ms; to_stopped = packets whose target does not run when the sample is taken; degree_bins[b] = "
+                    "(node, sample) pairs with min(packets addressed, 31) == b",
+            "packets": packets, "records": int(s["records"].sum()), "bytes": 16 * int(s["units"].sum()),
+            "to_stopped": to_down, "to_stopped_share": to_down / packets if packets else None,
+            "bytes_per_s_sent": rates["tx_stats"], "bytes_per_s_addressed": rates["rx_stats"],
+            "most_addressed_in_one_sample": int(s["max_packets"].max()) if len(s) else 0,
+            "degree_bins": s["degree_bins"].sum(axis=0).tolist() if len(s) else [],
+            "hottest_receivers": [{"node": int(r["id"]), "running": int(r["running"]), **{k: int(r["node"][k]) for k in _ffi.TRAFFIC_COLUMN_NAMES}}
+                                  for r in sim.traffic_top(10, 5)],
+            "rx_units_summary": {k: (summ[k].tolist() if summ[k].ndim else int(summ[k])) for k in summ.dtype.names}}
+
+
 def run_tracker(args, sim, lib):
     """The --tracker run: everything the host does happens between two long sim_step calls."""
     import math
@@ -331,6 +364,7 @@ def run_tracker(args, sim, lib):
     ledger = ledger.json() if ledger else None
     spread = spread.json() if spread else None
     detect = detect_json(args, sim) if args.detect else None
+    traffic = traffic_json(args, sim) if args.traffic else None
 
     def rounds(name):
         return [r[name] - t for t, r in done_ev if r[name] != NEVER]
@@ -366,6 +400,8 @@ def run_tracker(args, sim, lib):
         out["spread"] = spread
     if detect:
         out["detect"] = detect
+    if traffic:
+        out["traffic"] = traffic
     json.dump(out, open(args.out, "w"), indent=None if series or census or roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "sim_step_calls", "crashes", "events", "false_positives", "model_bound_drops", "ops_dropped_no_slot", "wall_s")}), "->", args.out)
     print(json.dumps({"rounds_to_99": out["rounds_to"]["99"], "detection": out["detection"]}))
@@ -408,6 +444,7 @@ def main():
     ap.add_argument("--ledger", type=int, default=0, metavar="PERIOD", help="--tracker: follow the first 64 user events with rumour ledgers, sampled behind every PERIOD-th tick (include/serf_sim_ledger.h), and put their summaries into the JSON")
     ap.add_argument("--spread", type=int, default=0, metavar="PERIOD", help="--tracker: follow the first 64 user events with spread maps, latched behind every PERIOD-th tick (include/serf_sim_spread.h), and put their arrival histograms and unreached counts into the JSON")
     ap.add_argument("--detect", type=int, default=0, metavar="PERIOD", help="judge every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_detect.h): the episodes of every crash and every accusation of the run, their summary into the JSON")
+    ap.add_argument("--traffic", type=int, default=0, metavar="PERIOD", help="meter the gossip packets per sender and per target on the device behind every PERIOD-th tick (include/serf_sim_traffic.h): per-node byte percentiles and the ten hottest receivers into the JSON")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.ledger and not args.tracker:
@@ -415,7 +452,7 @@ def main():
     if args.spread and not args.tracker:
         ap.error("--spread follows the rumours of a --tracker run")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r12_config4_detect.json" if args.detect else "r13_config4_spread.json" if args.spread else "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
+        args.out = os.path.join(ROOT, "profiles", "r14_config4_traffic.json" if args.traffic else "r12_config4_detect.json" if args.detect else "r13_config4_spread.json" if args.spread else "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
 
     import numpy as np
     from serf_amd import _ffi
@@ -443,6 +480,8 @@ def main():
         sim.roll_start(0, args.roll, min(_ffi.ROLL_MAX_SAMPLES, 1 << 16), ROLL_TOP, _ffi.ROLL_BY_STALE)
     if args.detect:
         sim.detect_start(0, args.detect, min(_ffi.DETECT_MAX_SAMPLES, 1 << 16), 1 << 20)
+    if args.traffic:
+        sim.traffic_start(0, args.traffic, min(_ffi.TRAFFIC_MAX_SAMPLES, 1 << 16))
     if args.tracker:
         return run_tracker(args, sim, lib)
     rng = np.random.default_rng(5)
@@ -498,7 +537,7 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect", "spread")},
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect", "spread", "traffic")},
         "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
@@ -529,6 +568,8 @@ def main():
         out["roll"] = roll_json(args, sim)
     if args.detect:
         out["detect"] = detect_json(args, sim)
+    if args.traffic:
+        out["traffic"] = traffic_json(args, sim)
     json.dump(out, open(args.out, "w"), indent=None if args.series or args.census or args.roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "churn_events", "rounds_to_99", "model_bound_drops", "ops_dropped_no_slot", "failure_detector", "wall_s")}), "->", args.out)
 
