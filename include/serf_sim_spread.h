@@ -29,7 +29,7 @@
  * period above 1 an arrival is the first SAMPLED tick at which the node had it.
  *
  * Out of scope: sharded handles (shard_count > 1, SIM_CF_FORCE_SHARDED) — every call below returns SIM_ESTATE on such a
- * handle (vshards > 1 on a handle that holds every node is one handle and is supported); who infected whom.
+ * handle (vshards > 1 on a handle that holds every node is one handle and is supported); who infected whom (that is include/serf_sim_tree.h).
  */
 #ifndef SERF_SIM_SPREAD_H
 #define SERF_SIM_SPREAD_H

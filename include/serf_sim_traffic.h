@@ -41,7 +41,7 @@
  * the sampled ticks only.
  *
  * Out of scope: sharded handles (shard_count > 1, SIM_CF_FORCE_SHARDED) — every call below returns SIM_ESTATE on such a
- * handle (vshards > 1 on a handle that holds every node is one handle and is supported); who infected whom.
+ * handle (vshards > 1 on a handle that holds every node is one handle and is supported); who infected whom (that is include/serf_sim_tree.h).
  */
 #ifndef SERF_SIM_TRAFFIC_H
 #define SERF_SIM_TRAFFIC_H

@@ -388,6 +388,59 @@ def traffic_rates(nodes, samples, interval_ms=200):
     return out
 
 
+# include/serf_sim_tree.h: rumour tree (per record identity and node: the arrival, the node whose packet brought the rumour, the hop
+# count from the origin, latched behind every tick).  The ninth extension: a version of its own, bound only when the loaded library
+# exports it
+TREE_SYMBOLS = ("tree_start", "tree_count", "tree_read", "tree_stop", "tree_links", "tree_summary", "tree_path", "tree_top", "tree_version")
+TREE_HEADER_WORDS, TREE_ENTRY_WORDS, TREE_MAX, TREE_MAX_SAMPLES = 8, 8, 64, 1 << 20
+TREE_BINS, TREE_SUMMARY_WORDS, TREE_TOP_MAX, TREE_NONE = 32, 72, 64, 0xFFFFFFFF
+# a sample's header, one entry's record, one node's link, a ranked node and one entry's summary as numpy records: the tables of
+# include/serf_sim_tree.h ("id" of an entry = key | kind << 32)
+TREE_HEADER_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("n", "<u8"), ("new", "<u8"), ("new_orphans", "<u8"), ("copies", "<u8"),
+                              ("fresh", "<u8"), ("reserved", "<u8")])
+TREE_ENTRY_DTYPE = np.dtype([("id", "<u8"), ("val", "<u8"), ("new", "<u8"), ("new_orphans", "<u8"), ("reached", "<u8"), ("orphans", "<u8"),
+                             ("copies", "<u8"), ("fresh", "<u8")])
+TREE_LINK_DTYPE = np.dtype([("arrival", "<u4"), ("parent", "<u4"), ("hop", "<u4"), ("children", "<u4")])
+TREE_RANK_DTYPE = np.dtype([("id", "<u4"), ("running", "<u4"), ("link", TREE_LINK_DTYPE)])
+TREE_SUMMARY_DTYPE = np.dtype([("id", "<u8"), ("val", "<u8"), ("reached", "<u8"), ("orphans", "<u8"), ("depth", "<u8"), ("hop_sum", "<u8"),
+                               ("most_children", "<u8"), ("most_children_id", "<u8"), ("hop_bins", "<u8", (TREE_BINS,)),
+                               ("children_bins", "<u8", (TREE_BINS,))])
+assert TREE_HEADER_DTYPE.itemsize == 8 * TREE_HEADER_WORDS and TREE_ENTRY_DTYPE.itemsize == 8 * TREE_ENTRY_WORDS
+assert TREE_LINK_DTYPE.itemsize == 16 and TREE_RANK_DTYPE.itemsize == 24 and TREE_SUMMARY_DTYPE.itemsize == 8 * TREE_SUMMARY_WORDS
+
+
+class TreeLink(C.Structure):
+    _fields_ = [("arrival", C.c_uint32), ("parent", C.c_uint32), ("hop", C.c_uint32), ("children", C.c_uint32)]
+
+
+class TreeRank(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("running", C.c_uint32), ("link", TreeLink)]
+
+
+def tree_split(words, n):
+    """[samples * (8 + 8 * n)] words -> (headers[samples], records[samples][n])."""
+    return sample_split(words, TREE_HEADER_DTYPE, TREE_ENTRY_DTYPE, n)
+
+
+def tree_hops(links, qs=(50, 90, 99, 100)):
+    """The hop-count percentiles and the share of orphans of one entry's tree, from every node's link (TREE_LINK_DTYPE, as
+    Sim.tree_links returns them): a dict with "reached", "orphans", "orphan_share" (orphans / reached, 0.0 when nobody is
+    reached), "depth", "mean_hop" and "percentiles" — for every q of qs (0 < q <= 100) the smallest hop h such that at least
+    q % of the reached nodes have one <= h (the nearest-rank percentile: a hop count that occurs), None when nobody is reached."""
+    links = np.asarray(links)
+    got = links[links["arrival"] != 0]
+    hop = np.sort(got["hop"].astype(np.int64))
+    pct = {}
+    for q in qs:
+        if not 0 < q <= 100:
+            raise ValueError(f"percentile {q} outside (0, 100]")
+        rank = -(-int(round(q * 1000)) * len(hop) // 100000)            # ceil(q / 100 * len) in integers (q to three decimals)
+        pct[q] = int(hop[max(1, rank) - 1]) if len(hop) else None
+    orphans = int((got["parent"] == TREE_NONE).sum())
+    return {"reached": len(got), "orphans": orphans, "orphan_share": orphans / len(got) if len(got) else 0.0,
+            "depth": int(hop[-1]) if len(hop) else 0, "mean_hop": float(hop.mean()) if len(hop) else 0.0, "percentiles": pct}
+
+
 class LedgerEntry(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("key", C.c_uint32), ("val", C.c_uint64)]
 
@@ -547,7 +600,7 @@ class SimLib:
             fn = getattr(self.dll, prefix + name)  # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             self.f[name] = fn
-        # the seven extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
+        # the nine extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
         # bound whole or not at all
         count = (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)])
         read = (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)])
@@ -622,9 +675,20 @@ class SimLib:
                 "traffic_summary": (C.c_int, [H, u32, u32, vp]),
                 "traffic_version": (u32, []),
             }),
+            ("tree", "has_tree", {
+                "tree_start": (C.c_int, [H, C.POINTER(SpreadEntry), u32, u32, u32]),
+                "tree_count": count,
+                "tree_read": read,
+                "tree_stop": stop,
+                "tree_links": (C.c_int, [H, u32, u32, u32, vp]),
+                "tree_summary": (C.c_int, [H, vp]),
+                "tree_path": (C.c_int, [H, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u32)]),
+                "tree_top": (C.c_int, [H, u32, u32, vp]),
+                "tree_version": (u32, []),
+            }),
         ]
         assert [tuple(sigs) for _, _, sigs in ext] == [TRACK_SYMBOLS, SERIES_SYMBOLS, CENSUS_SYMBOLS, ROLL_SYMBOLS, LEDGER_SYMBOLS,
-                                                           DETECT_SYMBOLS, SPREAD_SYMBOLS, TRAFFIC_SYMBOLS]
+                                                           DETECT_SYMBOLS, SPREAD_SYMBOLS, TRAFFIC_SYMBOLS, TREE_SYMBOLS]
         self.ext = {}   # group -> exported
         for group, attr, sigs in ext:
             self.ext[group] = all(hasattr(self.dll, prefix + name) for name in sigs)
@@ -684,6 +748,10 @@ class SimLib:
     def traffic_version(self):
         """SIM_TRAFFIC_VERSION of include/serf_sim_traffic.h, or None when the library has no traffic meter."""
         return self.f["traffic_version"]() if self.has_traffic else None
+
+    def tree_version(self):
+        """SIM_TREE_VERSION of include/serf_sim_tree.h, or None when the library has no rumour tree."""
+        return self.f["tree_version"]() if self.has_tree else None
 
 
 class Sim:
@@ -1196,6 +1264,65 @@ class Sim:
         out = np.zeros(1, TRAFFIC_SUMMARY_DTYPE)
         self._ck(self._ext_fn("traffic", "summary")(self.h, column, bin_width, out.ctypes.data), "sim_traffic_summary")
         return out[0]
+
+    # ---- rumour tree (include/serf_sim_tree.h) ----
+    def tree_start(self, entries=(), first_tick=0, capacity=1 << 12):
+        """Starts a rumour tree of `entries` ((kind, key, ltime) triples of kinds K_JOIN .. K_QUERY, 64 at most): behind every
+        tick t >= first_tick, until `capacity` samples are held (a first_tick that has passed means "now"), every running node
+        that has applied an entry's rumour and has no arrival for it yet gets arrival = t + 1, as its parent the smallest
+        sender among the packets with the rumour that the sample before saw addressed to it, and hop = the parent's + 1 (an
+        orphan, hop 0, without such a parent)."""
+        fn = self._ext_fn("tree", "start")
+        self._ck(fn(self.h, spread_entries(entries), len(entries), first_tick, capacity), "sim_tree_start")
+        self._tree_n = len(entries)
+
+    def tree_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        return self._sample_count("tree")
+
+    def tree_read(self, first=0, n=None):
+        """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as (headers, records): numpy
+        arrays of TREE_HEADER_DTYPE [n] and TREE_ENTRY_DTYPE [n][entries]; waits for the handle's stream."""
+        return self._sample_read("tree", first, n, TREE_HEADER_DTYPE, TREE_ENTRY_DTYPE, getattr(self, "_tree_n", 1))
+
+    def tree_stop(self):
+        """Ends the tree and frees the planes and the samples."""
+        self._sample_stop("tree")
+
+    def tree_links(self, entry, first_node=0, count=None):
+        """The links {arrival, parent, hop, children} of nodes first_node .. first_node + count - 1 (count = None: up to the
+        last node) in the tree of `entry` as a numpy array of TREE_LINK_DTYPE; waits for the handle's stream."""
+        if count is None:
+            count = max(0, self.cfg.n_nodes - first_node)
+        out = np.zeros(max(1, count), TREE_LINK_DTYPE)
+        self._ck(self._ext_fn("tree", "links")(self.h, entry, first_node, count, out.ctypes.data), "sim_tree_links")
+        return out[:count]
+
+    def tree_summary(self):
+        """Every entry's summary as a numpy array of TREE_SUMMARY_DTYPE [entries]: reached, orphans, depth, the sum of the
+        hops, the most children and the smallest id that has them, the histograms of min(hop, 31) and min(children, 31) over
+        the reached nodes; waits for the handle's stream."""
+        out = np.zeros(max(1, getattr(self, "_tree_n", 1)), TREE_SUMMARY_DTYPE)
+        self._ck(self._ext_fn("tree", "summary")(self.h, out.ctypes.data), "sim_tree_summary")
+        return out[:getattr(self, "_tree_n", 1)]
+
+    def tree_path(self, entry, node, cap=None):
+        """(ids, total): the chain node, parent, grandparent ... up to its orphan — the first `cap` ids (cap = None: all) —
+        and its length hop + 1 (0 for a node without an arrival); waits for the handle's stream."""
+        if cap is None:
+            cap = self.cfg.n_nodes
+        ids = np.zeros(max(1, cap), np.uint32)
+        got, total = C.c_uint32(), C.c_uint32()
+        self._ck(self._ext_fn("tree", "path")(self.h, entry, node, ids.ctypes.data if cap else None, cap, C.byref(got), C.byref(total)),
+                 "sim_tree_path")
+        return ids[:got.value], total.value
+
+    def tree_top(self, entry, top_k=10):
+        """ALL nodes ranked by their children in the tree of `entry` descending, ties by ascending id: the first top_k as a
+        numpy array of TREE_RANK_DTYPE (records beyond n_nodes: id 0xFFFFFFFF and zeros); waits for the handle's stream."""
+        top = np.zeros(max(1, top_k), TREE_RANK_DTYPE)
+        self._ck(self._ext_fn("tree", "top")(self.h, entry, top_k, top.ctypes.data), "sim_tree_top")
+        return top[:top_k]
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

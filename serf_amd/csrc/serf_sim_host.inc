@@ -34,7 +34,7 @@ struct SplitArr {
   LazyPlanes lz;
 };
 enum { SP_VIEW = 0, SP_EV = 1, SP_Q = 2, SP_N = 3 };  // (the order of SIM_ARR_VIEW .. SIM_ARR_QRING and of the image's sections)
-enum { OB_SERIES = 0, OB_CENSUS = 1, OB_ROLL = 2, OB_LEDGER = 3, OB_DETECT = 4, OB_SPREAD = 5, OB_TRAFFIC = 6, OB_N = 7 };  // the periodic observers, in the order their samples follow a tick on the stream
+enum { OB_SERIES = 0, OB_CENSUS = 1, OB_ROLL = 2, OB_LEDGER = 3, OB_DETECT = 4, OB_SPREAD = 5, OB_TRAFFIC = 6, OB_TREE = 7, OB_N = 8 };  // the periodic observers, in the order their samples follow a tick on the stream
 // Function-local device scratch: freed when it goes out of scope — behind whatever stream synchronisation stands before that.
 template <typename T>
 struct DevScratch {
@@ -344,7 +344,7 @@ static int rings_need(sim_handle* h) {
 #define EV_CAP (1u << 20)
 
 // ---- what the observers share on the host (the device part: serf_sim_observe.inc; it stands here because it needs the handle) ----
-// trackers, series, census, roll, ledger, detection log, spread map and traffic meter watch a handle that holds every node, between ticks
+// trackers, series, census, roll, ledger, detection log, spread map, traffic meter and rumour tree watch a handle that holds every node, between ticks
 static int observer_usable(const sim_handle* h) {
   if (!h) return SIM_EINVAL;
   if (h->d.sharded || h->in_tick) return SIM_ESTATE;
@@ -395,7 +395,7 @@ static void sampler_close(Sampler& S) {  // (the caller has waited for the sampl
   S.d_buf = nullptr;
 }
 
-// ---- the periodic observers' frame: series, census, roll, ledger, detection log, spread map and traffic meter differ in their kernels and in nothing below ----
+// ---- the periodic observers' frame: series, census, roll, ledger, detection log, spread map, traffic meter and rumour tree differ in their kernels and in nothing below ----
 // A periodic observer while it runs: its samples and, in the struct derived from it, the scratch and the parameters of its kernels.
 struct Observer {
   Sampler smp;

@@ -26,6 +26,7 @@
 #include "../../include/serf_sim_ledger.h"
 #include "../../include/serf_sim_spread.h"
 #include "../../include/serf_sim_traffic.h"
+#include "../../include/serf_sim_tree.h"
 #include "../../include/serf_sim_detect.h"
 #include "wire.hpp"
 
@@ -450,6 +451,61 @@ class Cluster {
     check(sim_traffic_summary(h_, column, bin_width, reinterpret_cast<uint64_t*>(&s)), "sim_traffic_summary");
     return s;
   }
+  // rumour tree (include/serf_sim_tree.h): behind every tick every running node that has applied one of up to 64 rumours and has no
+  // arrival for it yet gets arrival = tick + 1, as its parent the smallest sender among the packets with the rumour that the sample
+  // before saw addressed to it, and hop = the parent's + 1 (an orphan, hop 0, without one) — who infected whom.  A sample says what
+  // it latched, how many copies travel and how many of them are still useful; the tree is read by node (tree_links), summed up
+  // (tree_summary), by chain (tree_path) or ranked by children (tree_top).  HIP library only.
+  struct TreeSample {
+    uint64_t header[SIM_TREE_HEADER_WORDS];  // now, running, n, latched now, of them orphans, copies in flight, fresh carriers, 0
+    struct Entry { uint64_t id, val, latched, new_orphans, reached, orphans, copies, fresh; };  // id = key | kind << 32
+    std::vector<Entry> entries;              // in the order they were given
+  };
+  struct TreeSummary {
+    uint64_t id, val, reached, orphans, depth, hop_sum, most_children, most_children_id, hop_bins[SIM_TREE_BINS], children_bins[SIM_TREE_BINS];
+  };
+  void tree_start(const std::vector<sim_tree_entry>& e, uint32_t first_tick = 0, uint32_t capacity = 1u << 12) {
+    check(sim_tree_start(h_, e.data(), (uint32_t)e.size(), first_tick, capacity), "sim_tree_start");
+    tree_n_ = (uint32_t)e.size();
+  }
+  // (samples taken, dropped with the buffer full); waits for nothing
+  std::pair<uint32_t, uint32_t> tree_count() const { return sample_count(sim_tree_count, "sim_tree_count"); }
+  std::vector<TreeSample> tree_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    const uint32_t ne = tree_n_;
+    return sample_read<TreeSample>(sim_tree_count, sim_tree_read, "sim_tree", first, n, SIM_TREE_HEADER_WORDS + (size_t)ne * SIM_TREE_ENTRY_WORDS,
+                                   [ne](const uint64_t* w, TreeSample& s) { unpack(w, ne, s.header, s.entries); });
+  }
+  void tree_stop() { check(sim_tree_stop(h_), "sim_tree_stop"); }
+  // {arrival, parent, hop, children} of nodes first_node .. in the tree of `entry` (default: up to the last node)
+  std::vector<sim_tree_link> tree_links(uint32_t entry, uint32_t first_node = 0, uint32_t count = 0xFFFFFFFFu) {
+    if (count == 0xFFFFFFFFu) count = n_ > first_node ? n_ - first_node : 0;
+    std::vector<sim_tree_link> out(count ? count : 1);
+    check(sim_tree_links(h_, entry, first_node, count, out.data()), "sim_tree_links");
+    out.resize(count);
+    return out;
+  }
+  std::vector<TreeSummary> tree_summary() {
+    std::vector<TreeSummary> out(tree_n_ ? tree_n_ : 1);
+    check(sim_tree_summary(h_, reinterpret_cast<uint64_t*>(out.data())), "sim_tree_summary");
+    out.resize(tree_n_);
+    return out;
+  }
+  // (the chain node, parent, grandparent ... up to its orphan, the first `cap` ids; its length hop + 1, 0 without an arrival)
+  std::pair<std::vector<uint32_t>, uint32_t> tree_path(uint32_t entry, uint32_t node, uint32_t cap = 0xFFFFFFFFu) {
+    if (cap > n_) cap = n_;
+    std::vector<uint32_t> ids(cap ? cap : 1);
+    uint32_t got = 0, total = 0;
+    check(sim_tree_path(h_, entry, node, ids.data(), cap, &got, &total), "sim_tree_path");
+    ids.resize(got);
+    return {ids, total};
+  }
+  // ALL nodes ranked by their children in the tree of `entry` descending, ties by ascending id: the first top_k
+  std::vector<sim_tree_rank> tree_top(uint32_t entry, uint32_t top_k = 10) {
+    std::vector<sim_tree_rank> out(top_k ? top_k : 1);
+    check(sim_tree_top(h_, entry, top_k, out.data()), "sim_tree_top");
+    out.resize(top_k);
+    return out;
+  }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;
@@ -468,6 +524,9 @@ class Cluster {
   uint32_t roll_top_ = 1;    // top_k of the running roll: likewise
   uint32_t ledger_n_ = 1;    // entries of the running ledger: likewise
   uint32_t spread_n_ = 1;    // entries of the running spread map: likewise
+  uint32_t tree_n_ = 1;      // entries of the running rumour tree: likewise
+  static_assert(sizeof(TreeSample::Entry) == 8 * SIM_TREE_ENTRY_WORDS && sizeof(TreeSummary) == 8 * SIM_TREE_SUMMARY_WORDS,
+                "an entry's record is eight words, its summary seventy-two");
   static_assert(sizeof(SpreadSample::Entry) == 8 * SIM_SPREAD_ENTRY_WORDS && sizeof(SpreadSummary) == 8 * SIM_SPREAD_SUMMARY_WORDS,
                 "an entry's record is eight words, its summary forty");
   static_assert(sizeof(LedgerSample::Entry) == 8 * SIM_LEDGER_ENTRY_WORDS, "an entry's record is eight words");

@@ -54,6 +54,11 @@ episode of the run (per kind and outcome the count and the median and 99th perce
 (cumulative counters and the three latency histograms) and the log's counts.  Without the flag nothing about the run changes.
 The run of profiles/r12_config4_detect.json (--tracker --detect 1): see profiles/r12_detect.md.
 
+`--tree` (with --tracker): a RUMOUR TREE (include/serf_sim_tree.h) of the first 64 user events the trackers follow, a tree per burst
+as for --spread, latched behind every tick: who infected whom.  Per event the JSON gets, under "tree", the reached nodes and the
+orphans among them, the depth, the hop histogram and percentiles (_ffi.tree_hops) and the ten nodes with the most children.  See
+profiles/r15_tree.md.
+
 `--traffic PERIOD`: a TRAFFIC METER (include/serf_sim_traffic.h) behind every PERIOD-th tick: per node the gossip packets, records and
 wire bytes it sent and had addressed to it.  The run's JSON gets, under "traffic", the bytes per second sent and addressed per node
 (median, 99th percentile, max and the 99th-percentile-to-median ratio; _ffi.traffic_rates), the ten nodes the most bytes were addressed
@@ -195,6 +200,53 @@ class SpreadRun:
                         "everything beyond; arrival_percentiles = the tick by which that share of the reached nodes had it"}
 
 
+class TreeRun:
+    """--tree: one rumour tree per burst of user events until TREE_MAX rumours have been followed."""
+
+    def __init__(self, args, sim):
+        from serf_amd import _ffi
+        self.ffi, self.args, self.sim = _ffi, args, sim
+        self.followed, self.open_at, self.done, self.dropped = 0, None, [], 0
+
+    def close(self):
+        if self.open_at is None:
+            return
+        taken, dropped = self.sim.tree_count()
+        self.dropped += dropped
+        for i, s in enumerate(self.sim.tree_summary()):
+            bins = [int(x) for x in s["hop_bins"]]
+            while bins and not bins[-1]:
+                bins.pop()
+            hops = self.ffi.tree_hops(self.sim.tree_links(i))
+            self.done.append({"injected_at": self.open_at, "samples": int(taken), "key": int(s["id"] & 0xFFFFFFFF), "ltime": int(s["val"]),
+                              "reached": int(s["reached"]), "orphans": int(s["orphans"]), "orphan_share": hops["orphan_share"],
+                              "depth": int(s["depth"]), "mean_hop": hops["mean_hop"],
+                              "hop_percentiles": {str(q): v for q, v in hops["percentiles"].items()}, "hop_histogram": bins,
+                              "most_children": [{"node": int(r["id"]), "running": int(r["running"]), "children": int(r["link"]["children"]),
+                                                 "hop": int(r["link"]["hop"]), "arrival": int(r["link"]["arrival"])}
+                                                for r in self.sim.tree_top(i, 10)]})
+        self.sim.tree_stop()
+        self.open_at = None
+
+    def burst(self, t, rumours):
+        """rumours: (kind, key, ltime) of the events about to be injected at tick t."""
+        if self.followed >= self.ffi.TREE_MAX:
+            return
+        self.close()
+        take = rumours[:self.ffi.TREE_MAX - self.followed]
+        self.sim.tree_start(take, 0, 1 << 12)
+        self.open_at, self.followed = int(t), self.followed + len(take)
+
+    def json(self):
+        self.close()
+        return {"rumours": self.done, "dropped": self.dropped,
+                "what": "include/serf_sim_tree.h: per followed user event (the first 64, a tree per burst, ended by the next burst): reached = "
+                        "nodes with an arrival; orphans = of them without a parent (the origin, push-pull deliveries); depth = the largest hop "
+                        "count; hop_histogram = reached nodes by hop count, the 32nd bin taking everything beyond; hop_percentiles = the hop "
+                        "count within which that share of the reached nodes lies; most_children = the ten nodes that were the first to tell "
+                        "the most others"}
+
+
 def census_json(args, sim):
     """The headers of the run's census, one list per field of _ffi.CENSUS_HEADER_DTYPE, and the records of the state at the end."""
     taken, dropped = sim.census_count()
@@ -302,6 +354,7 @@ def run_tracker(args, sim, lib):
     ci = 0
     ledger = LedgerRun(args, sim) if args.ledger else None
     spread = SpreadRun(args, sim) if args.spread else None
+    tree = TreeRun(args, sim) if args.tree else None
     t0 = time.perf_counter()
     stretches = 0
 
@@ -349,6 +402,8 @@ def run_tracker(args, sim, lib):
                 ledger.burst(t, [(sp.a, sp.b, sp.ltime) for sp in specs])
             if spread:
                 spread.burst(t, [(sp.a, sp.b, sp.ltime) for sp in specs])
+            if tree:
+                tree.burst(t, [(sp.a, sp.b, sp.ltime) for sp in specs])
             for node, key in keys:
                 sim.user_event(node, key, 64)
         sim.step(min(every, total - t))     # ONE call per stretch; nothing is read back inside it
@@ -363,6 +418,7 @@ def run_tracker(args, sim, lib):
     roll = roll_json(args, sim) if args.roll else None
     ledger = ledger.json() if ledger else None
     spread = spread.json() if spread else None
+    tree = tree.json() if tree else None
     detect = detect_json(args, sim) if args.detect else None
     traffic = traffic_json(args, sim) if args.traffic else None
 
@@ -398,6 +454,8 @@ def run_tracker(args, sim, lib):
         out["ledger"] = ledger
     if spread:
         out["spread"] = spread
+    if tree:
+        out["tree"] = tree
     if detect:
         out["detect"] = detect
     if traffic:
@@ -444,6 +502,7 @@ def main():
     ap.add_argument("--ledger", type=int, default=0, metavar="PERIOD", help="--tracker: follow the first 64 user events with rumour ledgers, sampled behind every PERIOD-th tick (include/serf_sim_ledger.h), and put their summaries into the JSON")
     ap.add_argument("--spread", type=int, default=0, metavar="PERIOD", help="--tracker: follow the first 64 user events with spread maps, latched behind every PERIOD-th tick (include/serf_sim_spread.h), and put their arrival histograms and unreached counts into the JSON")
     ap.add_argument("--detect", type=int, default=0, metavar="PERIOD", help="judge every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_detect.h): the episodes of every crash and every accusation of the run, their summary into the JSON")
+    ap.add_argument("--tree", action="store_true", help="--tracker: follow the first 64 user events with rumour trees, latched behind every tick (include/serf_sim_tree.h), and put their hop histograms, depths, orphans and the ten nodes with the most children into the JSON")
     ap.add_argument("--traffic", type=int, default=0, metavar="PERIOD", help="meter the gossip packets per sender and per target on the device behind every PERIOD-th tick (include/serf_sim_traffic.h): per-node byte percentiles and the ten hottest receivers into the JSON")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -451,8 +510,10 @@ def main():
         ap.error("--ledger follows the rumours of a --tracker run")
     if args.spread and not args.tracker:
         ap.error("--spread follows the rumours of a --tracker run")
+    if args.tree and not args.tracker:
+        ap.error("--tree follows the rumours of a --tracker run")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r14_config4_traffic.json" if args.traffic else "r12_config4_detect.json" if args.detect else "r13_config4_spread.json" if args.spread else "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
+        args.out = os.path.join(ROOT, "profiles", "r15_config4_tree.json" if args.tree else "r14_config4_traffic.json" if args.traffic else "r12_config4_detect.json" if args.detect else "r13_config4_spread.json" if args.spread else "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
 
     import numpy as np
     from serf_amd import _ffi
@@ -537,7 +598,7 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect", "spread", "traffic")},
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect", "spread", "traffic", "tree")},
         "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
