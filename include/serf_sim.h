@@ -70,7 +70,7 @@ extern "C" {
 #define SIM_EDEVICE -3   /* HIP runtime error (no GPU, launch failure)                 */
 #define SIM_ENOSLOT -4   /* no free view slot for a new active subject                 */
 #define SIM_ESTATE -5    /* call not valid in the node's SerfState (api.rs:422-437)    */
-#define SIM_ERANGE -6    /* output buffer too small                                    */
+#define SIM_ERANGE -6    /* output buffer too small; a step beyond SIM_TICK_MAX        */
 #define SIM_ETOOBIG -7   /* user event / query larger than the configured limit        */
 
 /* MemberStatus — serf-core/src/types/member.rs:54-87 (same numeric values). */
@@ -186,7 +186,19 @@ typedef struct sim_packet {
  *   bits: [0] known  [3:1] MemberStatus  [5:4] swim state  [7:6] buffered intent (0 none,1 join,2 leave)
  *         [10:8] nconf  [31:11] stamp (tick, 21 bits: suspicion start / intent wall time / leave time)
  *   ltime: status_time when known, buffered intent ltime otherwise (base.rs:1835-1866)
+ * The stamp is the tick modulo 2^21 and every age is formed modulo 2^21, (now - stamp) & 0x1FFFFF: the tick may cross any
+ * multiple of 2^21.  An age is therefore only right while it is below 2^21, so every interval or timeout of sim_config that
+ * an age or a deadline is measured against must be < SIM_INTERVAL_LIMIT (sim_create refuses others).  What stays a property
+ * of the model: with the Reaper off (reap_interval == 0) nothing erases a failed or left member, and an entry that nobody
+ * touches for a multiple of 2^21 ticks looks young again (to gossip_to_the_dead, to a Reaper switched on by a later image).
  */
+#define SIM_STAMP_BITS 21u
+#define SIM_INTERVAL_LIMIT (1u << SIM_STAMP_BITS) /* intervals, timeouts and the suspicion table's entries stay below it */
+/* The last tick a handle may execute: 2^32 - 2^22 - 1.  Deadlines (suspicion timers, the Reaper's and a query's deadline,
+ * a slot's next recycling) are 32-bit sums, compared with `<`, with 0 for "no timer" and 0xFFFFFFFF for "never".  A deadline
+ * is at most now plus two intervals (a stamp no later than now, plus a timeout) and every interval is < 2^21, so no sum
+ * reaches 2^32 or the markers while now <= SIM_TICK_MAX (the margin is a factor of two). */
+#define SIM_TICK_MAX 0xFFBFFFFFull
 typedef struct sim_view {
   uint64_t ltime;
   uint32_t inc;
@@ -522,7 +534,11 @@ int sim_peek_packet(sim_handle* h, uint32_t node, uint32_t k, uint8_t* buf, size
  * SerfDelegate::notify_message (delegate.rs:157-315), the handlers it dispatches to
  * (base.rs:750-837, 972-1073, 1338-1373, 1442-1572), SerfDelegate::broadcast_messages
  * (delegate.rs:317-384) and memberlist's TransmitLimitedQueue / gossip fan-out (App. B.1-B.2).
- * Asynchronous on the handle's stream; sim_sync waits. */
+ * Asynchronous on the handle's stream; sim_sync waits.
+ * Ticks run from 0 to SIM_TICK_MAX.  sim_step checks the whole of n_ticks first: when its last tick would lie beyond
+ * SIM_TICK_MAX it returns SIM_ERANGE and executes nothing (the tick and the state are as they were); sim_step_begin does the
+ * same for its one tick.  Below the limit the tick may cross 2^21 and its multiples freely: stamps and ages are taken modulo
+ * 2^21 (sim_view), and sim_create bounds every interval accordingly. */
 int sim_step(sim_handle* h, uint32_t n_ticks);
 int sim_sync(sim_handle* h);
 int sim_tick(const sim_handle* h, uint64_t* tick);
@@ -713,7 +729,8 @@ int sim_step_end(sim_handle* h);
  * CANONICAL state — the arrays of sim_dump_state plus slot maps, liveness, running queries, the pending
  * operation schedule and the tick — so an image written by one implementation of this ABI restores into
  * another.  sim_snapshot with buf == NULL returns the size.  sim_restore needs a handle created with the
- * same sim_config (checked) that has not been stepped yet; un-drained events are not part of the image. */
+ * same sim_config (checked) that has not been stepped yet; un-drained events are not part of the image.  An image whose
+ * tick is beyond SIM_TICK_MAX is refused with SIM_EINVAL while it is validated: the handle stays the fresh one it was. */
 int sim_snapshot(sim_handle* h, void* buf, size_t cap_bytes, size_t* bytes);
 int sim_restore(sim_handle* h, const void* buf, size_t bytes);
 

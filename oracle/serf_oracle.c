@@ -1886,6 +1886,13 @@ static int cfg_check(const sim_config* c) {
     uint32_t A = (c->view_slots == 0 || c->view_slots >= c->n_nodes) ? c->n_nodes : c->view_slots;
     if (A > 65534u) return SIM_EINVAL;
   }
+  { /* ages are formed modulo 2^21 (the view entry's stamp), deadlines are 32-bit sums: whatever an age or a deadline is measured
+     * against stays below SIM_INTERVAL_LIMIT (the suspicion table's entries: swim_params' cap of 2 000 000) */
+    const uint32_t iv[] = {c->probe_interval, c->intent_timeout, c->leave_delay, c->reap_interval, c->reconnect_timeout, c->tombstone_timeout,
+                           c->queue_check_interval, c->push_pull_interval, c->recycle_interval, c->gossip_to_the_dead, c->reconnect_interval};
+    for (size_t i = 0; i < sizeof iv / sizeof iv[0]; ++i)
+      if (iv[i] >= SIM_INTERVAL_LIMIT) return SIM_EINVAL;
+  }
   return SIM_OK;
 }
 
@@ -2683,6 +2690,7 @@ int API(set_tags)(osim* s, uint32_t node, uint32_t tag_class) {
 
 int API(step)(osim* s, uint32_t n) {
   if (!s) return SIM_EINVAL;
+  if (n && s->tick + n - 1 > SIM_TICK_MAX) return SIM_ERANGE; /* the whole of n first: nothing is executed */
   for (uint32_t i = 0; i < n; ++i) {
     if (SHARDED(s)) { /* needs the host between begin and end when a cross-shard push-pull batch is due */
       uint32_t cls;
@@ -2899,6 +2907,7 @@ int API(restore)(osim* s, const void* buf, size_t bytes) {
   snap_header h;
   memcpy(&h, buf, sizeof h);
   if (h.magic != SNAP_MAGIC || h.abi != SIM_ABI_VERSION || memcmp(&h.cfg, &s->cfg, sizeof(sim_config))) return SIM_EINVAL;
+  if (h.tick > SIM_TICK_MAX) return SIM_EINVAL;
   { /* every section length before anything is written: an image that is refused leaves the handle the fresh one it was */
     const void* vptr[SNAP_SECTIONS];
     size_t vlen[SNAP_SECTIONS];
@@ -3241,6 +3250,7 @@ int API(recycle_apply)(osim* s, const sim_recycle_cand* agreed, uint32_t n) {
 int API(step_begin)(osim* s) {
   if (!s) return SIM_EINVAL;
   if (s->in_tick) return SIM_ESTATE;
+  if (s->tick > SIM_TICK_MAX) return SIM_ERANGE;
   if (SHARDED(s) && recycle_due(s)) return SIM_ESTATE; /* the host runs the pass first (it needs every shard) */
 
   step_begin(s);

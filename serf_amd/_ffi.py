@@ -15,6 +15,9 @@ import numpy as np
 P, Q, CKEYS, MAX_FANOUT = 4, 64, 6, 4
 Q_HOT = 16  # SIM_Q_HOT: the entries the HIP tick kernel keeps in registers
 DEFAULT_SEED = 0x5EEDC0DE5E4F0001
+STAMP_BITS = 21                             # SIM_STAMP_BITS: a view entry's stamp is the tick modulo 2^21
+INTERVAL_LIMIT = 1 << STAMP_BITS            # SIM_INTERVAL_LIMIT: every interval and timeout of the config stays below it
+TICK_MAX = (1 << 32) - (1 << 22) - 1        # SIM_TICK_MAX: the last tick a handle executes (a step beyond it: SIM_ERANGE)
 
 OK, EINVAL, ENOMEM, EDEVICE, ENOSLOT, ESTATE, ERANGE, ETOOBIG = 0, -1, -2, -3, -4, -5, -6, -7
 _ERR = {EINVAL: "SIM_EINVAL", ENOMEM: "SIM_ENOMEM", EDEVICE: "SIM_EDEVICE", ENOSLOT: "SIM_ENOSLOT",

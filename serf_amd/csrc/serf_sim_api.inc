@@ -1096,6 +1096,7 @@ int sim_restore(sim_handle* h, const void* buf, size_t bytes) {
   memcpy(&hd, buf, sizeof hd);
   if (hd.magic != SNAP_MAGIC || hd.abi != SIM_ABI_VERSION || memcmp(&hd.cfg, &h->cfg, sizeof(sim_config))) return SIM_EINVAL;
   // ---- pass 1: validate the header, every section length and what the kernels index with, before anything is touched ----
+  if (hd.tick > SIM_TICK_MAX) return SIM_EINVAL;                    // a handle executes no tick beyond it (include/serf_sim.h)
   if (hd.n_slots > d.A) return SIM_EINVAL;                          // reap_run / pp_merge walk a < n_slots
   if ((size_t)hd.n_pending_ops > bytes / sizeof(OpEnt)) return SIM_EINVAL;  // sizes a host allocation
   SnapSec sec[SNAP_SECTIONS];

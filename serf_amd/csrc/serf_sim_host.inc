@@ -219,6 +219,11 @@ static int cfg_check(const sim_config* c) {
     u32 A = (c->view_slots == 0 || c->view_slots >= c->n_nodes) ? c->n_nodes : c->view_slots;
     if (A > 65534u) return SIM_EINVAL;
   }
+  // ages are formed modulo 2^21 (the view entry's stamp) and deadlines are 32-bit sums below SIM_TICK_MAX's margin: everything an age
+  // or a deadline is measured against stays below SIM_INTERVAL_LIMIT (the suspicion table's entries: swim_params' cap)
+  for (u32 v : {c->probe_interval, c->intent_timeout, c->leave_delay, c->reap_interval, c->reconnect_timeout, c->tombstone_timeout,
+                c->queue_check_interval, c->push_pull_interval, c->recycle_interval, c->gossip_to_the_dead, c->reconnect_interval})
+    if (v >= SIM_INTERVAL_LIMIT) return SIM_EINVAL;
   return SIM_OK;
 }
 // Suspicion parameters in ticks (memberlist suspicion.go / util.go, SURVEY.md App. B.5); the same
@@ -243,6 +248,7 @@ static void swim_params(const sim_config* c, u32* swim, u32* k_out, u32 T[SIM_MA
     }
     T[i] = t > 2000000.0 ? 2000000u : (u32)t;
   }
+  static_assert(2000000u < SIM_INTERVAL_LIMIT, "a suspicion timeout is compared with an age taken modulo 2^21");
   *k_out = k;
 }
 

@@ -480,6 +480,7 @@ int sim_step_begin(sim_handle* h) {
   if (!h) return SIM_EINVAL;
   Dev& d = h->d;
   if (h->in_tick || (d.sharded && !h->bound)) return SIM_ESTATE;
+  if (h->tick > SIM_TICK_MAX) return SIM_ERANGE;  // the last tick a handle executes (include/serf_sim.h)
   if (h->xflag && *h->xflag) return SIM_ERANGE;  // a slab of the random fan-out's exchange (or a count byte, or the rows) overflowed
   if (h->xpending) { int rc = sim_exchange_wait(h); if (rc) return rc; }  // the packets of the round before have landed
   if (int rc = (d.swim && !d.sharded) ? begin_replay(h) : SIM_OK) return rc;
@@ -571,6 +572,7 @@ int sim_suspect_requests(sim_handle* h, uint32_t* out, uint32_t cap_pairs, uint3
 }
 int sim_step(sim_handle* h, uint32_t n_ticks) {
   if (!h) return SIM_EINVAL;
+  if (n_ticks && h->tick + n_ticks - 1 > SIM_TICK_MAX) return SIM_ERANGE;  // the whole of n_ticks first: nothing is executed
   Dev& d = h->d;
   if (d.sharded && !h->bound) return SIM_ESTATE;
   if (d.sharded && n_ticks > 1) return SIM_EINVAL;  // the caller has to move send -> recv between two ticks

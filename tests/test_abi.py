@@ -54,6 +54,18 @@ def test_struct_layouts_match_the_header(tmp_path):
     assert got[3:] == [112, 16, 32, 32, 48]
 
 
+def test_tick_domain_constants_match_the_header(tmp_path):
+    prog = tmp_path / "dom.c"
+    prog.write_text('#include <stdio.h>\n#include "serf_sim.h"\nint main(void){printf("%llu %u %u %d\\n",'
+                    "(unsigned long long)SIM_TICK_MAX,SIM_INTERVAL_LIMIT,SIM_STAMP_BITS,SIM_ERANGE);return 0;}\n")
+    exe = tmp_path / "dom"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(prog)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert got == [_ffi.TICK_MAX, _ffi.INTERVAL_LIMIT, _ffi.STAMP_BITS, _ffi.ERANGE]
+    assert got[:3] == [2 ** 32 - 2 ** 22 - 1, 2 ** 21, 21]
+    assert _ffi.make_config(64).reconnect_timeout < _ffi.INTERVAL_LIMIT   # the defaults (24 h of ticks) stay valid
+
+
 def test_product_has_no_cpu_fallback(hiplib):
     import torch
     if torch.cuda.is_available():

@@ -104,11 +104,8 @@ def test_packets_kept_at_the_sender_virtual_shards_and_chunks(oracle, hiplib, n,
     sc.assert_same_state(g, o, "final")
 
 
-@pytest.mark.parametrize("seed", list(range(48)))
-def test_random_configurations(oracle, hiplib, seed):
-    # a seeded sweep over the configuration space (size — ragged sizes included —, fan-out, virtual shards and chunks,
-    # view slots or dense views, ring sizes that are and are not powers of two, loss, load from idle to overload,
-    # SWIM / push-pull / reaper / queue checker / recycling on or off): digests after every tick, every array at the end
+def random_configuration(seed):
+    """The draw of test_random_configurations, a function of the seed alone: (n, kw, rate, dense)."""
     rng = np.random.default_rng(1000 + seed)
     v = int(rng.choice([1, 1, 2, 4]))
     c = int(rng.choice([0, 0, 2, 4])) if v > 1 or rng.random() < 0.3 else 0
@@ -129,11 +126,20 @@ def test_random_configurations(oracle, hiplib, seed):
               join_sync=bool(rng.random() < 0.5))
     kw.update(reconnect_interval=int(rng.choice([0, 0, 3, 7])) if swim else 0)  # Reconnector (drawn after everything else)
     kw.update(tcp_fallback=bool(swim and rng.random() < 0.4), nacks=bool(swim and rng.random() < 0.4))  # memberlist's fallback ping / nack accounting
+    rate = float(rng.choice([0.2, 0.8, 2.5]))
+    return n, kw, rate, dense
+
+
+@pytest.mark.parametrize("seed", list(range(48)))
+def test_random_configurations(oracle, hiplib, seed):
+    # a seeded sweep over the configuration space (size — ragged sizes included —, fan-out, virtual shards and chunks,
+    # view slots or dense views, ring sizes that are and are not powers of two, loss, load from idle to overload,
+    # SWIM / push-pull / reaper / queue checker / recycling on or off): digests after every tick, every array at the end
+    n, kw, rate, dense = random_configuration(seed)
     try:
         g, o = pair(oracle, hiplib, n, **kw)
     except _ffi.SimError:
         pytest.skip(f"configuration rejected by both sides: n={n} {kw}")
-    rate = float(rng.choice([0.2, 0.8, 2.5]))
     ops = sc.schedule(n, 40, rate=rate, seed=seed, max_member_subjects=12 if not dense else min(n // 2, 30))
     sc.apply_schedule(g, ops)
     sc.apply_schedule(o, ops)
@@ -147,14 +153,8 @@ def test_random_configurations(oracle, hiplib, seed):
     assert g.cluster_stats()["ops_dropped"] == o.cluster_stats()["ops_dropped"]
 
 
-@pytest.mark.parametrize("seed", list(range(32)))
-def test_random_fanout_kRandomNodes(oracle, hiplib, seed):
-    # SIM_CF_RANDOM_FANOUT: memberlist's literal kRandomNodes (App. B.2) — uniform targets, no replacement, variable in-degree —
-    # in the PRODUCT: the tick's fan-out graph is built two ticks ahead by the library's own two-level bucket sort (rf_*
-    # kernels), the packets stay in their senders' cells and every receiver pulls the ones its CSR row names.  Seeded sweep: tiny clusters (fewer other nodes than the fan-out: slots without a target), ragged and block-sized
-    # ones, dense and slotted views, SWIM / loss / gossip_to_the_dead / push-pull / reaper / recycling / Reconnector on or off,
-    # packets of 1 - 4 pages (seeds 16 ..); digests after every tick, every array at the end, a checkpoint in the middle that
-    # goes through the canonical (sender-indexed) inbox and back, both ways.
+def random_fanout_configuration(seed):
+    """The draw of test_random_fanout_kRandomNodes, a function of the seed alone: (n, kw, rate, dense)."""
     rng = np.random.default_rng(9000 + seed)
     n = int([2, 3, 5, 96, 200, 1000, 2048, 4096][seed % 8])
     dense = n <= 600 and rng.random() < 0.5
@@ -173,6 +173,18 @@ def test_random_fanout_kRandomNodes(oracle, hiplib, seed):
         rate = float(rng.choice([1.0, 2.5, 5.0]))
     if n >= 2048 and seed % 3 == 0:
         kw.update(vshards=4)   # (r4) ONE handle that holds a cluster of 4 virtual shards: what a 4-shard run is compared with
+    return n, kw, rate, dense
+
+
+@pytest.mark.parametrize("seed", list(range(32)))
+def test_random_fanout_kRandomNodes(oracle, hiplib, seed):
+    # SIM_CF_RANDOM_FANOUT: memberlist's literal kRandomNodes (App. B.2) — uniform targets, no replacement, variable in-degree —
+    # in the PRODUCT: the tick's fan-out graph is built two ticks ahead by the library's own two-level bucket sort (rf_*
+    # kernels), the packets stay in their senders' cells and every receiver pulls the ones its CSR row names.  Seeded sweep: tiny clusters (fewer other nodes than the fan-out: slots without a target), ragged and block-sized
+    # ones, dense and slotted views, SWIM / loss / gossip_to_the_dead / push-pull / reaper / recycling / Reconnector on or off,
+    # packets of 1 - 4 pages (seeds 16 ..); digests after every tick, every array at the end, a checkpoint in the middle that
+    # goes through the canonical (sender-indexed) inbox and back, both ways.
+    n, kw, rate, dense = random_fanout_configuration(seed)
     g, o = pair(oracle, hiplib, n, **kw)
     ops = sc.schedule(n, 40, rate=rate, seed=seed, max_member_subjects=max(1, min(n // 2, 12 if not dense else 30)))
     sc.apply_schedule(g, ops)

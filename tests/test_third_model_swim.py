@@ -40,7 +40,7 @@ def _packets(sim, n, fanout, PG=PG):
     return out
 
 
-def run(sim, n, ops, ticks, joined, **kw):
+def run(sim, n, ops, ticks, joined, t0=0, **kw):
     fanout = kw["fanout"]
     PG = kw.get("pkt_records", 4 * globals()["PG"]) // 4        # pages of a packet: 4 records each
     par = tms.Params(n, fanout, kw["probe_interval"], kw.get("suspicion_mult", 4), kw.get("suspicion_max_mult", 6), kw.get("indirect_checks", 3),
@@ -52,12 +52,13 @@ def run(sim, n, ops, ticks, joined, **kw):
                      tcp_fallback=kw.get("tcp_fallback", False), nacks=kw.get("nacks", False), gossip_to_the_dead=kw.get("gossip_to_the_dead", 0),
                      join_sync=kw.get("join_sync", False), prune_delay=kw.get("prune_delay", False))
     model = tms.Cluster(par, RING_EV, RING_Q, joined)
+    model.tick = t0                                             # the model counts in Python integers: no wrap at 2^21 or 2^32
     by_tick = {}
-    for o in ops:
+    for o in ((o[0] + t0,) + tuple(o[1:]) for o in ops):
         by_tick.setdefault(o[0], []).append(o[1:])
         sim.inject(*o)
     seen_kinds = set()
-    for t in range(ticks):
+    for t in range(t0, t0 + ticks):
         model.step(by_tick.get(t, ()))
         sim.step(1)
         rows = sim.dump(_ffi.ARR_ROWS)
@@ -97,7 +98,7 @@ def run(sim, n, ops, ticks, joined, **kw):
                     if ml[0] == tms.ML_SUSPECT:
                         conf = x.susp[s][1]
                         assert (bits >> 8) & 7 == len(conf) - 1 and [int(c) for c in e["conf"][:len(conf)]] == conf, f"{w} subject {s}: confirmers"
-                        assert (bits >> 11) == x.susp[s][0], f"{w} subject {s}: suspicion start"
+                        assert (bits >> 11) == x.susp[s][0] & 0x1FFFFF, f"{w} subject {s}: suspicion start"
                 else:
                     it = x.intents.get(s)
                     assert not (bits & 1) and s not in x.ml, f"{w} subject {s}"
