@@ -471,6 +471,61 @@ static int observer_now(sim_handle* h, size_t words, u64* host, Launch launch) {
   return SIM_OK;
 }
 
+// The tail of a read of what an observer keeps on the device (a map, a tree): launch() enqueues its kernels behind the samples enqueued so
+// far; the stream is synchronised before the caller's scratch is freed, also when the launch failed.
+template <typename Launch>
+static int observer_settle(sim_handle* h, Launch launch) {
+  int rc = launch();
+  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == SIM_OK) rc = SIM_EDEVICE;
+  return rc;
+}
+// A read that yields a list of node ids: launch(d_ids, room, d_total) writes the first `room` = min(cap, N) ids and the number of all
+// into ONE scratch; the total comes back, then the ids there are (no list is longer than the nodes)
+template <typename Launch>
+static int observer_read_ids(sim_handle* h, u32* ids, u32 cap, u32* n_out, u32* total, Launch launch) {
+  const u32 room = std::min<u32>(cap, h->d.N);
+  DevScratch<u32> d_ids;  // [room] ids, then the total
+  if (int rc = d_ids.alloc((size_t)room + 1)) return rc;
+  if (int rc = observer_settle(h, [&]() -> int { return launch(d_ids.get(), room, d_ids.get() + room); })) return rc;
+  u32 tot = 0;
+  HCHECK(hipMemcpy(&tot, d_ids.get() + room, 4, hipMemcpyDeviceToHost));
+  const u32 got = std::min(tot, room);
+  if (got) HCHECK(hipMemcpy(ids, d_ids.get(), (size_t)got * 4, hipMemcpyDeviceToHost));
+  *n_out = got;
+  *total = tot;
+  return SIM_OK;
+}
+// A read that yields a ranking (rank_candidates / rank_merge, serf_sim_observe.inc): the lists of ceil(Nl / BLOCK) workgroups — keys of
+// key_words words, records of rec_words —, launch(ckey, crec, d_top, G) enqueues the two kernels, top_k records come back
+template <typename Launch>
+static int observer_read_top(sim_handle* h, u32 top_k, u32 key_words, u32 rec_words, void* top, Launch launch) {
+  const size_t G = ((size_t)h->d.Nl + BLOCK - 1) / BLOCK;
+  DevScratch<u64> d_ckey, d_crec, d_top;
+  if (int rc = d_ckey.alloc(G * top_k * key_words)) return rc;
+  if (int rc = d_crec.alloc(G * top_k * rec_words)) return rc;
+  if (int rc = d_top.alloc((size_t)top_k * rec_words)) return rc;
+  if (int rc = observer_settle(h, [&]() -> int { return launch(d_ckey.get(), d_crec.get(), d_top.get(), (u32)G); })) return rc;
+  HCHECK(hipMemcpy(top, d_top.get(), (size_t)top_k * rec_words * 8, hipMemcpyDeviceToHost));
+  return SIM_OK;
+}
+// sim_step_end, tick h->tick - 1 enqueued: where the packets it sent lie (Flight, serf_sim_observe.inc).  rows: the observer walks the
+// packets addressed to a node — under kRandomNodes the graph of that tick then stands in front of the stream (rf_ready)
+static int rf_ready(sim_handle* h, u64 s);
+static int flight_fill(sim_handle* h, bool rows, Flight& f) {
+  const Dev& d = h->d;
+  const u64 t = h->tick - 1;  // the tick that sent the packets in flight
+  f.rcsr = f.rsrc = nullptr;
+  f.rcap = 0;
+  if (rows && d.rfan) {
+    if (int rc = rf_ready(h, t)) return rc;
+    f.rcsr = h->rf_rcsr[t % 3]; f.rsrc = h->rf_rsrc[t % 3];
+    f.rcap = d.f * d.Nl;
+  }
+  f.cur = (u32)(h->tick & 1);
+  f.nslot = d.rfan ? d.f : h->prev.feff;  // (h->prev: the parameters of the tick that just ended)
+  return SIM_OK;
+}
+
 // Everything the handle holds, whatever sim_create, sim_exchange_init or an observer got as far as setting up.  Nothing is given back
 // while a stream may still use it: all three streams first.
 sim_handle::~sim_handle() {

@@ -11,8 +11,8 @@
 //                        chain is compared: two entries may differ in val only.  A running node walks the groups of sort keys its
 //                        count says are in use and the payload of each listed slot (the canonical record as canon_qrec assembles it:
 //                        transmits from the key, kind from the payload's low byte); every node walks the packets it sent last tick
-//                        where they lie (obox[cur] / omap[cur], 64- or 48-byte cells), all three uint4 of every page of every distinct
-//                        packet, weighted by the slots that map to it.  Hits are integer LDS adds into [n][LED_CNT] 32-bit counters;
+//                        (sent_packets, serf_sim_observe.inc), all three uint4 of every page of every distinct packet, weighted by the
+//                        slots that map to it.  Hits are integer LDS adds into [n][LED_CNT] 32-bit counters;
 //                        holders goes through a 64-bit mask per lane, once per node.  A workgroup sees Nl / LEDGER_GRID nodes — 16 Ki at
 //                        the 16 Mi a handle can have — of SIM_Q = 64 records with 63 transmits at most: 2^26, far below 2^32; in flight
 //                        a node sends fanout * pkt_records <= 2^7 record copies: 2^21.  The header's sums are wave reductions.  Every
@@ -48,7 +48,6 @@ struct LedTab {
   uint8_t next[SIM_LEDGER_MAX];  // entry -> the next one of its chain, or LED_NONE
   u32 n, pad;
 };
-static_assert(sizeof(LedTab) % 4 == 0, "staged into LDS word by word");
 
 struct LedDevP {
   const LedTab* tab;
@@ -58,8 +57,7 @@ struct LedDevP {
   u32 G;             // workgroups of the count kernel
   u32 n;             // entries
   u32 now;           // sim_tick after the sampled tick
-  u32 cur;           // parity of the cells that hold the packets in flight (obox[cur] / omap[cur])
-  u32 nslot;         // fan-out slots that carry packets: f (random fan-out), feff of the tick that sent them (bijection)
+  Flight fl;         // the packets in flight (cur and nslot: the ledger reads no rows)
 };
 
 // the entry a record (kind, key, val) matches, or LED_NONE; val: 64 bits of a queued record, 48 of one on the wire — SUSPECT / DEAD: the
@@ -73,13 +71,32 @@ __device__ static inline u32 ledger_find(const LedTab& t, u32 kind, u32 key, u64
 }
 
 __global__ __launch_bounds__(BLOCK) void ledger_count_kernel(Dev d, LedDevP p) {
+  struct Sent {  // sent_packets' visitor: every record of a distinct packet weighs as many slots as map to it; a repeat slot adds nothing
+    const LedTab& tab;
+    u32* cnt;
+    u32 &fl_all, &pkts;
+    u32 any;
+    __device__ void page(u32, u32 wgt, const uint4* cell) {
+      const uint4 ck = ld4(cell), cl = ld4(cell + 1), ch = ld4(cell + 2);
+      const u32 kw[4] = {ck.x, ck.y, ck.z, ck.w}, lw[4] = {cl.x, cl.y, cl.z, cl.w}, hw[4] = {ch.x, ch.y, ch.z, ch.w};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const u32 kind = SIM_META_KIND(hw[r]) & 7u;
+        if (!kind) continue;  // (an empty record is all zero)
+        any = 1;
+        fl_all += wgt;
+        const u32 e = ledger_find(tab, kind, kw[r], (u64)lw[r] | ((u64)(hw[r] >> 16) << 32));
+        if (e != LED_NONE) atomicAdd(&cnt[e * LED_CNT + (LE_FLIGHT - LE_HOLD)], wgt);  // (LDS)
+      }
+    }
+    __device__ void packet(u32, u32 wgt) { pkts += any ? wgt : 0u; any = 0; }
+    __device__ void repeat(u32, u32) {}
+  };
   __shared__ LedTab tab;
   __shared__ u32 cnt[SIM_LEDGER_MAX * LED_CNT];
   __shared__ unsigned long long hdr[SIM_LEDGER_HEADER_WORDS];
   {
-    const u32* src = reinterpret_cast<const u32*>(p.tab);
-    u32* dst = reinterpret_cast<u32*>(&tab);
-    for (u32 i = threadIdx.x; i < sizeof(LedTab) / 4; i += BLOCK) dst[i] = src[i];
+    lds_stage(tab, p.tab);
     for (u32 i = threadIdx.x; i < SIM_LEDGER_MAX * LED_CNT; i += BLOCK) cnt[i] = 0;
     if (threadIdx.x < SIM_LEDGER_HEADER_WORDS) hdr[threadIdx.x] = 0;
   }
@@ -88,16 +105,11 @@ __global__ __launch_bounds__(BLOCK) void ledger_count_kernel(Dev d, LedDevP p) {
   u32 q_all = 0, tx_all = 0, fl_all = 0, pkts = 0;    // per lane, reduced over the wave once, at the end
   const size_t per_pass = (size_t)gridDim.x * BLOCK;
   const size_t passes = ((size_t)d.Nl + per_pass - 1) / per_pass;
-  const size_t cu4 = d.rfan ? RF_CELL_U4 : PK_U4;
   for (size_t it = 0; it < passes; ++it) {  // whole waves stay together: the ballot below needs every lane
     const size_t l = it * per_pass + (size_t)blockIdx.x * BLOCK + threadIdx.x;
     const bool in = l < d.Nl;
     uint4 r1 = make_uint4(0, 0, 0, 0), r2 = r1;
-    u32 jw = 0xFFFFFFFFu;
-    if (in) {
-      r1 = ld4(&d.R1[l]); r2 = ld4(&d.R2[l]);
-      jw = d.rfan ? d.obox[p.cur][l * RF_CELL_U4 + 3u].x : d.omap[p.cur][l];  // slot -> cell of the packets this node sent
-    }
+    if (in) { r1 = ld4(&d.R1[l]); r2 = ld4(&d.R2[l]); }
     const bool up = in && (r1.z & SIM_RF_UP);
     c_up += (u32)__popcll(__ballot(up));
     // ---- the node's queue: keys ascending in groups of four, the records in the payload slots the keys name ----
@@ -129,36 +141,9 @@ __global__ __launch_bounds__(BLOCK) void ledger_count_kernel(Dev d, LedDevP p) {
       }
     }
     // ---- the packets this node sent last tick, where they lie: a distinct packet weighs as many slots as map to it ----
-    if (jw != 0xFFFFFFFFu) {
-      for (u32 k = 0; k < p.nslot; ++k) {
-        const u32 jb = (jw >> (8u * k)) & 0xFFu;  // first page << 2 | pages - 1
-        if (jb == 0xFFu) continue;
-        bool again = false;
-        u32 wgt = 0;
-        for (u32 q = 0; q < p.nslot; ++q) {
-          const bool same = ((jw >> (8u * q)) & 0xFFu) == jb;
-          again |= same && q < k;
-          wgt += same ? 1u : 0u;
-        }
-        if (again) continue;
-        u32 any = 0;
-        const u32 np = min(jb & 3u, d.PG - 1u);
-        for (u32 pg = 0; pg <= np && (jb >> 2) + pg < d.fp; ++pg) {  // (never beyond the node's fp cells)
-          const uint4* cell = d.obox[p.cur] + ((size_t)((jb >> 2) + pg) * d.Nl + l) * cu4;
-          const uint4 ck = ld4(cell), cl = ld4(cell + 1), ch = ld4(cell + 2);
-          const u32 kw[4] = {ck.x, ck.y, ck.z, ck.w}, lw[4] = {cl.x, cl.y, cl.z, cl.w}, hw[4] = {ch.x, ch.y, ch.z, ch.w};
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const u32 kind = SIM_META_KIND(hw[r]) & 7u;
-            if (!kind) continue;  // (an empty record is all zero)
-            any = 1;
-            fl_all += wgt;
-            const u32 e = ledger_find(tab, kind, kw[r], (u64)lw[r] | ((u64)(hw[r] >> 16) << 32));
-            if (e != LED_NONE) atomicAdd(&cnt[e * LED_CNT + (LE_FLIGHT - LE_HOLD)], wgt);
-          }
-        }
-        pkts += any ? wgt : 0u;
-      }
+    if (in) {
+      Sent v = {tab, cnt, fl_all, pkts, 0u};
+      sent_packets(d, p.fl.cur, p.fl.nslot, l, v);
     }
   }
   // ---- the workgroup's column ----
@@ -268,8 +253,7 @@ static int ledger_launch(sim_handle* h, const LedScratch& s, u64* out) {
   p.G = (u32)std::min<size_t>(((size_t)d.Nl + BLOCK - 1) / BLOCK, LEDGER_GRID);
   p.n = s.n;
   p.now = (u32)h->tick;
-  p.cur = (u32)(h->tick & 1);
-  p.nslot = d.rfan ? d.f : h->prev.feff;  // (h->prev: the parameters of the tick that just ended, the one that sent the packets)
+  if (int rc = flight_fill(h, false, p.fl)) return rc;
   if (s.cs.n) {
     HCHECK(hipMemsetAsync(s.d_reach.get(), 0, (size_t)(s.cs.n + 1) * 8, h->stream));
     convergence_many_kernel<<<grid_for(d.Nl), BLOCK, 0, h->stream>>>(d, h->d_base, s.cs, s.d_reach.get());

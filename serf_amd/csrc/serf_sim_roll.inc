@@ -14,13 +14,12 @@
 //                        observer runs is a bit of upmap.  The six counts and lag stay in the lane's registers: an observer's record
 //                        needs no cross-lane step.  Behind the sweep the header's sums, maxima and bins go through LDS into the
 //                        workgroup's column of a partial matrix — integers throughout, no atomics on global memory, nothing to zero —
-//                        and the workgroup selects its own top_k candidates by key = score << 32 | (0xFFFFFFFF - id): keys are unique,
-//                        so round r is "the largest key below round r - 1's", which needs no marking.  A candidate carries its key and
-//                        all eight words of the record; a list shorter than top_k ends with key 0.  sim_roll_now may ask for every
-//                        node's record: then the lane stores its 64 bytes as well; a sampled roll writes no per-node array
-//   roll_fold_kernel     one workgroup: folds the partial rows into the header, counts the subjects, runs the same selection over the
-//                        workgroups' candidate lists (each sorted: the largest key of a list below the last one chosen is the first
-//                        below it) and writes the listed records, zeroing what stays unused
+//                        and the workgroup lists its own top_k candidates (rank_candidates, serf_sim_observe.inc) by key = score << 32 |
+//                        (0xFFFFFFFF - id): keys are unique.  A candidate carries its key and all eight words of the record.
+//                        sim_roll_now may ask for every node's record: then the lane stores its 64 bytes as well; a sampled roll
+//                        writes no per-node array
+//   roll_fold_kernel     one workgroup: folds the partial rows into the header, counts the subjects, merges the workgroups' candidate
+//                        lists (rank_merge) and writes the listed records, zeroing what stays unused
 // Their order is the stream's.  The host knows every sampled tick in advance: it passes the sample's place to the launches and reads nothing back.
 // A handle without a started roll never gets here (sim_step_end finds its entry of the observers' table null).
 #include "../../include/serf_sim_roll.h"
@@ -61,18 +60,6 @@ struct RollDevP {
 __device__ static inline u64 roll_score(const u64 w[SIM_ROLL_NODE_WORDS], u32 rank_by) {
   return rank_by == SIM_ROLL_BY_STALE ? w[RW_STALE] : rank_by == SIM_ROLL_BY_ACCUSED ? w[RW_FF] + w[RW_SUSP] : w[RW_SA];
 }
-// the workgroup's largest value of v; red: [2][BLOCK / 64], the halves taken in turn (one barrier a call: a wave that is two calls
-// ahead has passed the barrier of the call in between, which every wave reaches only behind its reads of this one)
-__device__ static inline u64 roll_group_max(u64 v, u64 (*red)[BLOCK / 64], u32 turn) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) red[turn & 1u][threadIdx.x >> 6] = v;
-  __syncthreads();
-  u64 m = 0;
-#pragma unroll
-  for (u32 q = 0; q < BLOCK / 64; ++q) { const u64 y = red[turn & 1u][q]; m = y > m ? y : m; }
-  return m;
-}
-
 __global__ __launch_bounds__(BLOCK) void roll_count_kernel(RollDevP p) {
   __shared__ u32 s_slot[ROLL_CHUNK];   // the chunk's allocated slots, ascending
   __shared__ u64 s_ltmax[ROLL_CHUNK];  // their references
@@ -181,24 +168,10 @@ __global__ __launch_bounds__(BLOCK) void roll_count_kernel(RollDevP p) {
   }
   __syncthreads();
   if (threadIdx.x < SIM_ROLL_HEADER_WORDS && roll_has_row(threadIdx.x)) p.part[(size_t)threadIdx.x * p.G + blockIdx.x] = acc[threadIdx.x];
-  // the workgroup's candidates: round r takes the largest key below round r - 1's
+  // the workgroup's candidates
   const u64 score = roll_score(w, p.rank_by);  // (0 for a node that does not run: never listed)
   const u64 key = score ? (score << 32) | (u64)(0xFFFFFFFFu - i) : 0ull;
-  u64 prev = ~0ull;
-  u64* ck = p.ckey + (size_t)blockIdx.x * p.top_k;
-  u32 r = 0;
-  for (; r < p.top_k; ++r) {  // (the same in every lane)
-    const u64 m = roll_group_max(key < prev ? key : 0ull, red, r);
-    if (!m) break;
-    if (key == m) {
-      u64* dst = p.crec + ((size_t)blockIdx.x * p.top_k + r) * SIM_ROLL_NODE_WORDS;
-      ck[r] = m;
-#pragma unroll
-      for (u32 k = 0; k < SIM_ROLL_NODE_WORDS; ++k) dst[k] = w[k];
-    }
-    prev = m;
-  }
-  if (r < p.top_k && threadIdx.x == 0) ck[r] = 0;
+  rank_candidates<SIM_ROLL_NODE_WORDS>(key, w, p.ckey, p.crec, p.top_k, red);
 }
 
 // one workgroup: the header out of the partial rows, the listed records out of the workgroups' candidates
@@ -219,34 +192,7 @@ __global__ __launch_bounds__(BLOCK) void roll_fold_kernel(RollDevP p) {
     c = (u32)wave_sum(c);
     if (!lane && c) atomicAdd(&hdr[RH_SUBJECTS], (unsigned long long)c);  // (LDS)
   }
-  u64* recs = p.out + SIM_ROLL_HEADER_WORDS;
-  u64 prev = ~0ull;
-  u32 r = 0;
-  for (; r < p.top_k; ++r) {  // (the same in every lane)
-    u64 best = 0;
-    size_t at = 0;
-    for (u32 g = threadIdx.x; g < p.G; g += BLOCK) {
-      const size_t base = (size_t)g * p.top_k;
-      for (u32 j = 0; j < p.top_k; ++j) {  // a list is sorted: its first key below prev is its largest below prev
-        const u64 k = p.ckey[base + j];
-        if (!k) break;
-        if (k < prev) {
-          if (k > best) { best = k; at = base + j; }
-          break;
-        }
-      }
-    }
-    const u64 m = roll_group_max(best, red, r);
-    if (!m) break;
-    if (best == m) {  // (keys are unique: one lane)
-      const u64* src = p.crec + at * SIM_ROLL_NODE_WORDS;
-      u64* dst = recs + (size_t)r * SIM_ROLL_NODE_WORDS;
-#pragma unroll
-      for (u32 k = 0; k < SIM_ROLL_NODE_WORDS; ++k) dst[k] = src[k];
-    }
-    prev = m;
-  }
-  for (u32 k = r * SIM_ROLL_NODE_WORDS + threadIdx.x; k < p.top_k * SIM_ROLL_NODE_WORDS; k += BLOCK) recs[k] = 0;
+  const u32 r = rank_merge<SIM_ROLL_NODE_WORDS>(p.ckey, p.crec, p.G, p.top_k, p.out + SIM_ROLL_HEADER_WORDS, red, FillZero());
   if (threadIdx.x == 0) {
     hdr[RH_TICK] = p.now;
     hdr[RH_LISTED] = (u64)r | ((u64)p.rank_by << 32);

@@ -3,25 +3,23 @@
 // bookkeeping, the entry points.
 //
 // Per sampled tick:
-//   spread_latch_kernel  a node per lane, grid-stride, SPREAD_GRID workgroups at most, whole waves kept together (the pass loop of
-//                        ledger_count_kernel).  The entries — uploaded at sim_spread_start, not per sample — are staged once per workgroup
-//                        in LDS.  Per (node, entry): one coalesced 4-byte read of the entry's plane of the map [n][Nl] and, for a running
-//                        node, ONE evaluation of the shared predicate (view_applied / bucket_holds, slot_of and the baseline, as
-//                        convergence_many_kernel uses them) — it yields `holds` and the latch alike, so the reach pass is not launched as
+//   spread_latch_kernel  a node per lane, grid-stride, SPREAD_GRID workgroups at most, whole waves kept together.  The entries —
+//                        uploaded at sim_spread_start, not per sample — are staged once per workgroup in LDS (lds_stage).  Per (node, entry): one coalesced 4-byte read of the entry's plane of the map [n][Nl] and, for a running
+//                        node, ONE evaluation of the shared predicate (rumour_held, serf_sim_observe.inc: view_applied / bucket_holds,
+//                        slot_of and the baseline, as convergence_many_kernel uses them) — it yields `holds` and the latch alike, so the reach pass is not launched as
 //                        well.  The plane is written only where a node latches.  Counts go through wave ballots and popcounts into LDS,
 //                        first / last through wave_min / wave_max and an LDS min / max.  Every workgroup writes its column of a partial
 //                        matrix [1 + SPR_ROWS n][G] as 64-bit words — no atomics on global memory, nothing to zero, the result does not
 //                        depend on order
 //   spread_fold_kernel   one wave per word of the sample: folds its row (fold_row), or — header words 3 .. 5 — the rows of every entry
-// The reads of the map (each behind a wait for the stream, on scratch of its own, the map untouched):
+// The reads of the map (each behind a wait for the stream — observer_settle —, on scratch of its own, the map untouched):
 //   spread_stat_kernel / spread_hist_kernel   the summary's two passes — the bins need `first` — in the pass loop above: counts by ballots,
 //                        a histogram [n][SIM_SPREAD_BINS] in LDS per workgroup, a column each; spread_scan_fold writes the words
 //   spread_unreached_kernel   ONE workgroup walks the nodes in chunks of BLOCK: a node's place in the list is the unreached of the chunks
 //                        before (carried), of the waves before (LDS) and of the lanes before (a ballot) — ascending id whatever order the
 //                        waves run in (detect_kernel's idiom)
 //   spread_late_kernel / spread_late_fold   a node per lane, a workgroup per BLOCK nodes; the record stays in the lane's registers; the
-//                        workgroup selects its top_k candidates, one workgroup selects among the lists (the roll's selection: keys are
-//                        unique, round r is "the largest key below round r - 1's") — here a key is a pair (score + 1, 0xFFFFFFFF - id):
+//                        ranking in two levels (rank_candidates / rank_merge) — here with the two-word key (score + 1, 0xFFFFFFFF - id):
 //                        missed, late_sum and the id together need more than 64 bits
 // A handle without a started map never gets here (sim_step_end finds its entry of the observers' table null).
 #include "../../include/serf_sim_spread.h"
@@ -47,7 +45,6 @@ struct SprTab {
   u64 ltime[SIM_SPREAD_MAX];
   u32 n, pad;
 };
-static_assert(sizeof(SprTab) % 4 == 0, "staged into LDS word by word");
 
 struct SprDevP {
   const SprTab* tab;
@@ -59,29 +56,12 @@ struct SprDevP {
   u32 now;     // sim_tick after the sampled tick
 };
 
-__device__ static inline void spread_stage(SprTab& tab, const SprTab* src_tab) {
-  const u32* src = reinterpret_cast<const u32*>(src_tab);
-  u32* dst = reinterpret_cast<u32*>(&tab);
-  for (u32 i = threadIdx.x; i < sizeof(SprTab) / 4; i += BLOCK) dst[i] = src[i];
-}
-// has node l (running) applied the rumour (kind, key, ltime)?  The predicate's one place of use besides convergence_many_kernel
-__device__ __forceinline__ static bool spread_holds(const Dev& d, const uint4* base, size_t l, u32 kind, u32 key, u64 ltime) {
-  if (kind == SIM_K_JOIN || kind == SIM_K_LEAVE) {
-    const u32 a = d.slot_of[key];
-    const uint4 e = a == NOSLOT ? base[(size_t)key * 2] : d.view[(size_t)a * d.Nl + l];
-    return view_applied(e, ltime);
-  }
-  const uint4* ring = kind == SIM_K_EVENT ? d.ering : d.qring;
-  const u32 idx = (u32)(ltime % (kind == SIM_K_EVENT ? d.Bev : d.Bq));
-  return bucket_holds(d, ring, kind == SIM_K_EVENT ? d.etail : d.qtail, idx, l, ring[(size_t)idx * d.Nl + l], key);
-}
-
 __global__ __launch_bounds__(BLOCK) void spread_latch_kernel(Dev d, const uint4* base, SprDevP p) {
   __shared__ SprTab tab;
   __shared__ u32 cnt[SIM_SPREAD_MAX * 4];  // new, reached, reached_up, holds
   __shared__ u32 lo[SIM_SPREAD_MAX], hi[SIM_SPREAD_MAX];
   __shared__ u32 s_up;
-  spread_stage(tab, p.tab);
+  lds_stage(tab, p.tab);
   for (u32 i = threadIdx.x; i < SIM_SPREAD_MAX * 4; i += BLOCK) cnt[i] = 0;
   if (threadIdx.x < SIM_SPREAD_MAX) { lo[threadIdx.x] = 0xFFFFFFFFu; hi[threadIdx.x] = 0; }
   if (threadIdx.x == 0) s_up = 0;
@@ -99,7 +79,7 @@ __global__ __launch_bounds__(BLOCK) void spread_latch_kernel(Dev d, const uint4*
       u32* cell = p.map + (size_t)e * d.Nl + l;
       u32 a = in ? *cell : 0u;
       const u64 id = tab.id[e];
-      const bool hit = up && spread_holds(d, base, l, (u32)(id >> 32), (u32)id, tab.ltime[e]);
+      const bool hit = up && rumour_held(d, base, l, (u32)(id >> 32), (u32)id, tab.ltime[e]);
       const bool latch = hit && a == 0u;
       if (latch) { *cell = p.now; a = p.now; }
       const u64 mn = __ballot(latch), mr = __ballot(a != 0u), mru = __ballot(a != 0u && up), mh = __ballot(hit);
@@ -281,27 +261,9 @@ struct SprLateP {
   u32 G;            // workgroups of the late kernel: ceil(Nl / BLOCK)
   u32 n, top_k, rank_by;
 };
-// a selection key: unique among the running nodes; s == 0: none
-struct SprKey { u64 s; u64 r; };
-__device__ static inline bool spr_less(SprKey a, SprKey b) { return a.s < b.s || (a.s == b.s && a.r < b.r); }
-// the workgroup's largest key; red: [2][BLOCK / 64], the halves taken in turn (roll_group_max)
-__device__ static inline SprKey spr_group_max(SprKey v, SprKey (*red)[BLOCK / 64], u32 turn) {
-  for (int o = 32; o > 0; o >>= 1) {
-    SprKey y;
-    y.s = __shfl_xor(v.s, o); y.r = __shfl_xor(v.r, o);
-    if (spr_less(v, y)) v = y;
-  }
-  if ((threadIdx.x & 63) == 0) red[turn & 1u][threadIdx.x >> 6] = v;
-  __syncthreads();
-  SprKey m = {0, 0};
-#pragma unroll
-  for (u32 q = 0; q < BLOCK / 64; ++q) { const SprKey y = red[turn & 1u][q]; if (spr_less(m, y)) m = y; }
-  return m;
-}
-
 __global__ __launch_bounds__(BLOCK) void spread_late_kernel(Dev d, SprLateP p) {
   __shared__ u32 first[SIM_SPREAD_MAX];
-  __shared__ SprKey red[2][BLOCK / 64];
+  __shared__ WideKey red[2][BLOCK / 64];
   if (threadIdx.x < SIM_SPREAD_MAX) first[threadIdx.x] = threadIdx.x < p.n ? (u32)p.stat[(size_t)threadIdx.x * 8u + SS_FIRST] : 0u;
   __syncthreads();
   const u32 i = blockIdx.x * BLOCK + threadIdx.x;  // the node
@@ -322,62 +284,19 @@ __global__ __launch_bounds__(BLOCK) void spread_late_kernel(Dev d, SprLateP p) {
 #pragma unroll
     for (u32 k = 0; k < SIM_SPREAD_NODE_WORDS; ++k) dst[k] = w[k];
   }
-  // the workgroup's candidates: round r takes the largest key below round r - 1's.  late_sum < 64 * 2^32, missed <= 64
-  SprKey key = {0, 0};
+  // the key: unique among the running nodes.  late_sum < 64 * 2^32, missed <= 64
+  WideKey key = {0, 0};
   if (up) {
     key.s = 1ull + (p.rank_by == SIM_SPREAD_BY_MISSED ? ((u64)missed << 40) | late_sum : (late_sum << 8) | (u64)missed);
     key.r = (u64)(0xFFFFFFFFu - i);
   }
-  SprKey prev = {~0ull, ~0ull};
-  u64* ck = p.ckey + (size_t)blockIdx.x * p.top_k * 2u;
-  const SprKey none = {0, 0};
-  u32 r = 0;
-  for (; r < p.top_k; ++r) {  // (the same in every lane)
-    const SprKey m = spr_group_max(spr_less(key, prev) ? key : none, red, r);
-    if (!m.s) break;
-    if (key.s == m.s && key.r == m.r) {
-      u64* dst = p.crec + ((size_t)blockIdx.x * p.top_k + r) * SIM_SPREAD_NODE_WORDS;
-      ck[2u * r] = m.s; ck[2u * r + 1u] = m.r;
-#pragma unroll
-      for (u32 k = 0; k < SIM_SPREAD_NODE_WORDS; ++k) dst[k] = w[k];
-    }
-    prev = m;
-  }
-  if (r < p.top_k && threadIdx.x == 0) ck[2u * r] = 0;
+  rank_candidates<SIM_SPREAD_NODE_WORDS>(key, w, p.ckey, p.crec, p.top_k, red);
 }
 
-// one workgroup: the same selection over the workgroups' candidate lists (each sorted: the largest key of a list below the last one
-// chosen is the first below it); writes the listed records, zeroing what stays unused
+// one workgroup: the lists merged; writes the listed records, zeroing what stays unused
 __global__ __launch_bounds__(BLOCK) void spread_late_fold(SprLateP p) {
-  __shared__ SprKey red[2][BLOCK / 64];
-  SprKey prev = {~0ull, ~0ull};
-  u32 r = 0;
-  for (; r < p.top_k; ++r) {  // (the same in every lane)
-    SprKey best = {0, 0};
-    size_t at = 0;
-    for (u32 g = threadIdx.x; g < p.G; g += BLOCK) {
-      const size_t b = (size_t)g * p.top_k;
-      for (u32 j = 0; j < p.top_k; ++j) {
-        const SprKey k = {p.ckey[(b + j) * 2u], 0};
-        if (!k.s) break;
-        const SprKey kk = {k.s, p.ckey[(b + j) * 2u + 1u]};
-        if (spr_less(kk, prev)) {
-          if (spr_less(best, kk)) { best = kk; at = b + j; }
-          break;
-        }
-      }
-    }
-    const SprKey m = spr_group_max(best, red, r);
-    if (!m.s) break;
-    if (best.s == m.s && best.r == m.r) {  // (keys are unique: one lane)
-      const u64* src = p.crec + at * SIM_SPREAD_NODE_WORDS;
-      u64* dst = p.top + (size_t)r * SIM_SPREAD_NODE_WORDS;
-#pragma unroll
-      for (u32 k = 0; k < SIM_SPREAD_NODE_WORDS; ++k) dst[k] = src[k];
-    }
-    prev = m;
-  }
-  for (u32 k = r * SIM_SPREAD_NODE_WORDS + threadIdx.x; k < p.top_k * SIM_SPREAD_NODE_WORDS; k += BLOCK) p.top[k] = 0;
+  __shared__ WideKey red[2][BLOCK / 64];
+  rank_merge<SIM_SPREAD_NODE_WORDS>(p.ckey, p.crec, p.G, p.top_k, p.top, red, FillZero());
 }
 
 // ---- host ----
@@ -437,14 +356,6 @@ struct SpreadState : Observer {  // samples of 8 + 8 n words
 };
 static inline SpreadState* spread_of(const sim_handle* h) { return static_cast<SpreadState*>(h->obs[OB_SPREAD]); }
 
-// The tail of a read of the map: launch() enqueues its kernels; the stream is synchronised before the caller's scratch is freed, also when
-// the launch failed.
-template <typename Launch>
-static int spread_run(sim_handle* h, Launch launch) {
-  int rc = launch();
-  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == SIM_OK) rc = SIM_EDEVICE;
-  return rc;
-}
 // the summary's first pass and its fold into out[n][stride] (the stream's order puts both behind the samples enqueued so far)
 static int spread_stat_launch(sim_handle* h, const SpreadState* s, SprScanP& p, u64* part, u64* out, u32 stride) {
   p.tab = s->d_tab.get(); p.map = s->d_map.get(); p.part = part; p.out = out;
@@ -501,7 +412,7 @@ int sim_spread_summary(sim_handle* h, uint32_t bin_width, uint64_t* out) {
   DevScratch<u64> part, d_out;
   if (int rc = part.alloc((size_t)SPR_HIST * s->n * G)) return rc;  // (SPR_HIST >= SPR_STAT: both passes' columns fit)
   if (int rc = d_out.alloc(words)) return rc;
-  int rc = spread_run(h, [&]() -> int {
+  int rc = observer_settle(h, [&]() -> int {
     SprScanP p;
     if (int lrc = spread_stat_launch(h, s, p, part.get(), d_out.get(), SIM_SPREAD_SUMMARY_WORDS)) return lrc;
     p.bin_width = bin_width;
@@ -522,22 +433,11 @@ int sim_spread_unreached(sim_handle* h, uint32_t entry, uint32_t* ids, uint32_t 
   const SpreadState* s = spread_of(h);
   if (!s) return SIM_ESTATE;
   if (entry >= s->n) return SIM_EINVAL;
-  const u32 room = std::min<u32>(cap, h->d.N);  // (no list is longer than the nodes)
-  DevScratch<u32> d_ids;  // [room] ids, then the total
-  if (int rc = d_ids.alloc((size_t)room + 1)) return rc;
-  int rc = spread_run(h, [&]() -> int {
-    spread_unreached_kernel<<<1, BLOCK, 0, h->stream>>>(h->d, s->d_map.get() + (size_t)entry * h->d.Nl, d_ids.get(), room, d_ids.get() + room);
+  return observer_read_ids(h, ids, cap, n_out, total, [&](u32* d_ids, u32 room, u32* d_total) -> int {
+    spread_unreached_kernel<<<1, BLOCK, 0, h->stream>>>(h->d, s->d_map.get() + (size_t)entry * h->d.Nl, d_ids, room, d_total);
     HCHECK(hipGetLastError());
     return SIM_OK;
   });
-  if (rc != SIM_OK) return rc;
-  u32 tot = 0;
-  HCHECK(hipMemcpy(&tot, d_ids.get() + room, 4, hipMemcpyDeviceToHost));
-  const u32 got = std::min(tot, room);
-  if (got) HCHECK(hipMemcpy(ids, d_ids.get(), (size_t)got * 4, hipMemcpyDeviceToHost));
-  *n_out = got;
-  *total = tot;
-  return SIM_OK;
 }
 
 int sim_spread_late(sim_handle* h, uint32_t top_k, uint32_t rank_by, sim_spread_node* top, sim_spread_node* nodes) {
@@ -545,23 +445,19 @@ int sim_spread_late(sim_handle* h, uint32_t top_k, uint32_t rank_by, sim_spread_
   if (!top || !top_k || top_k > SIM_SPREAD_TOP_MAX || rank_by > SIM_SPREAD_BY_LATE) return SIM_EINVAL;
   const SpreadState* s = spread_of(h);
   if (!s) return SIM_ESTATE;
-  const size_t G = spread_grid(h), G2 = ((size_t)h->d.Nl + BLOCK - 1) / BLOCK;
-  DevScratch<u64> part, d_stat, d_ckey, d_crec, d_top, d_nodes;
-  if (int rc = part.alloc((size_t)SPR_STAT * s->n * G)) return rc;
+  DevScratch<u64> part, d_stat, d_nodes;
+  if (int rc = part.alloc((size_t)SPR_STAT * s->n * spread_grid(h))) return rc;
   if (int rc = d_stat.alloc((size_t)s->n * 8)) return rc;
-  if (int rc = d_ckey.alloc(G2 * top_k * 2)) return rc;
-  if (int rc = d_crec.alloc(G2 * top_k * SIM_SPREAD_NODE_WORDS)) return rc;
-  if (int rc = d_top.alloc((size_t)top_k * SIM_SPREAD_NODE_WORDS)) return rc;
   if (nodes)
     if (int rc = d_nodes.alloc((size_t)h->d.Nl * SIM_SPREAD_NODE_WORDS)) return rc;
-  int rc = spread_run(h, [&]() -> int {
+  int rc = observer_read_top(h, top_k, 2u, SIM_SPREAD_NODE_WORDS, top, [&](u64* ckey, u64* crec, u64* d_top, u32 G) -> int {
     SprScanP sp;
     if (int lrc = spread_stat_launch(h, s, sp, part.get(), d_stat.get(), 8)) return lrc;
     SprLateP p;
-    p.map = s->d_map.get(); p.stat = d_stat.get(); p.ckey = d_ckey.get(); p.crec = d_crec.get();
+    p.map = s->d_map.get(); p.stat = d_stat.get(); p.ckey = ckey; p.crec = crec;
     p.nodes = nodes ? d_nodes.get() : nullptr;
-    p.top = d_top.get();
-    p.G = (u32)G2;
+    p.top = d_top;
+    p.G = G;
     p.n = s->n; p.top_k = top_k; p.rank_by = rank_by;
     spread_late_kernel<<<p.G, BLOCK, 0, h->stream>>>(h->d, p);
     spread_late_fold<<<1, BLOCK, 0, h->stream>>>(p);
@@ -569,7 +465,6 @@ int sim_spread_late(sim_handle* h, uint32_t top_k, uint32_t rank_by, sim_spread_
     return SIM_OK;
   });
   if (rc != SIM_OK) return rc;
-  HCHECK(hipMemcpy(top, d_top.get(), (size_t)top_k * sizeof *top, hipMemcpyDeviceToHost));
   if (nodes) HCHECK(hipMemcpy(nodes, d_nodes.get(), (size_t)h->d.N * sizeof *nodes, hipMemcpyDeviceToHost));
   return SIM_OK;
 }

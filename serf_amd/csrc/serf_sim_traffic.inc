@@ -3,26 +3,25 @@
 // bookkeeping, the entry points.
 //
 // Per sampled tick, in stream order:
-//   traffic_send_kernel  a node per lane, grid-stride, TRAFFIC_GRID workgroups at most, whole waves kept together (the pass loop of
-//                        ledger_count_kernel).  The node's map word and the third uint4 (value high bits + meta) of every page of every
+//   traffic_send_kernel  a node per lane, grid-stride, TRAFFIC_GRID workgroups at most, whole waves kept together.  The sender walk, written
+//                        out here (see the kernel): the node's map word and the third uint4 (value high bits + meta) of every page of every
 //                        DISTINCT packet it sent, where they lie (obox[cur], 64- or 48-byte cells): records and units of the packet, 5 + 7
 //                        bits, copied to every slot that maps to it — 16 bits a slot, a 64-bit summary a node, written as one coalesced 8-byte
 //                        store (psum[Nl]).  The tx columns of the map; the header's sums through wave reductions, the record bins through LDS
-//   traffic_recv_kernel  a node per lane, the same pass loop.  The packets addressed to the node: kRandomNodes, the row rsrc[rcsr[l] ..
-//                        rcsr[l + 1]) of the graph of the sampled tick (entries sender * 4 + slot; rf_ready puts the graph in front of the
-//                        stream); the bijection, the feff sources through fan_source_g.  Per packet ONE scattered 8-byte read of psum[sender]
+//   traffic_recv_kernel  a node per lane, the same pass loop.  The packets addressed to the node (recv_packets; flight_fill puts the
+//                        graph of the sampled tick in front of the stream under kRandomNodes).  Per packet ONE scattered 8-byte read of psum[sender]
 //                        and the slot's 16 bits of it.  The rx columns, rx_peak, rx_down; the in-degree histogram through LDS; the two
 //                        maxima travel as (value << 32) | ~id, so that one max yields the smallest id at the largest value
 //   traffic_fold_kernel  one wave per word of the sample: folds its row (fold_row) into the sample's slot
 // Both count kernels write their workgroup's column of ONE partial matrix [TRF_ROWS][G] as 64-bit words — no atomics on global memory,
 // nothing to zero, every figure an integer, the result does not depend on order.  The map is [8][Nl] uint32_t, a plane per column: every
 // access of a wave is one contiguous run.
-// The reads of the map (each behind a wait for the stream — spread_run —, on scratch of its own, the map untouched):
+// The reads of the map (each behind a wait for the stream — observer_settle —, on scratch of its own, the map untouched):
 //   traffic_nodes_kernel  a slice of the eight planes transposed into 32-byte records
 //   traffic_stat_kernel   one column: sum, max with the smallest id, min, non-zero, the histogram — ONE pass (no bin needs a figure of
 //                         the pass itself, unlike the spread map's delays), its columns folded by traffic_stat_fold
-//   traffic_top_kernel / traffic_top_fold   the roll's selection in two levels: keys (value << 32) | (0xFFFFFFFF - id) are unique, round r
-//                         takes the largest key below round r - 1's; every node has a key (ALL nodes are ranked)
+//   traffic_top_kernel / traffic_top_fold   the ranking in two levels (rank_candidates / rank_merge) by (value << 32) | (0xFFFFFFFF - id):
+//                         every node has a key (ALL nodes are ranked)
 // A handle without a started meter never gets here (sim_step_end finds its entry of the observers' table null).
 #include "../../include/serf_sim_traffic.h"
 
@@ -50,26 +49,14 @@ struct TrfDevP {
   u32* map;         // [8][Nl]
   u64* part;        // [TRF_ROWS][G]: every workgroup of the two count kernels writes its column
   u64* out;         // the sample's slot: 64 words
-  const u32* rcsr;  // kRandomNodes: the graph of the sampled tick, [Nl + 1] / [rcap]
-  const u32* rsrc;
-  u32 rcap;
+  Flight fl;        // the packets of the sampled tick, its graph's rows included
   u32 G;            // workgroups of the count kernels
   u32 now;          // sim_tick after the sampled tick
-  u32 cur;          // parity of the cells that hold the packets in flight (obox[cur] / omap[cur])
-  u32 nslot;        // fan-out slots that carry packets: f (random fan-out), feff of the tick that sent them (bijection)
   u32 samples;      // samples accumulated in the map, this one included
 };
 
-// lane-wise maximum over the workgroup into LDS (the wave's first, then one LDS atomic a wave)
-__device__ static inline void trf_lds_max(unsigned long long* dst, u64 v) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0 && v) atomicMax(dst, (unsigned long long)v);
-}
-__device__ static inline void trf_lds_sum(unsigned long long* dst, u64 v) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
+// The sender walk written out: sent_packets (serf_sim_observe.inc) with a visitor made this kernel 10 % slower on the MI355X (its slot loops
+// are unrolled for the tree's per-slot registers; profiles/observer_kit.md).  A change to the walk there has to be made here as well.
 __global__ __launch_bounds__(BLOCK) void traffic_send_kernel(Dev d, TrfDevP p) {
   __shared__ unsigned long long acc[TRS_REC];
   __shared__ u32 bins[SIM_TRAFFIC_REC_BINS];
@@ -83,11 +70,11 @@ __global__ __launch_bounds__(BLOCK) void traffic_send_kernel(Dev d, TrfDevP p) {
   for (size_t it = 0; it < passes; ++it) {  // whole waves stay together (the reductions behind the loop need every lane)
     const size_t l = it * per_pass + (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (l >= d.Nl) continue;
-    const u32 jw = d.rfan ? d.obox[p.cur][l * RF_CELL_U4 + 3u].x : d.omap[p.cur][l];  // slot -> cell of the packets this node sent
+    const u32 jw = d.rfan ? d.obox[p.fl.cur][l * RF_CELL_U4 + 3u].x : d.omap[p.fl.cur][l];  // slot -> cell of the packets this node sent
     u64 sum = 0;
     u32 n_p = 0, n_r = 0, n_u = 0;
     if (jw != 0xFFFFFFFFu) {
-      for (u32 k = 0; k < p.nslot; ++k) {
+      for (u32 k = 0; k < p.fl.nslot; ++k) {
         const u32 jb = (jw >> (8u * k)) & 0xFFu;  // first page << 2 | pages - 1
         if (jb == 0xFFu) continue;
         u32 fld = 0;
@@ -98,7 +85,7 @@ __global__ __launch_bounds__(BLOCK) void traffic_send_kernel(Dev d, TrfDevP p) {
           u32 r_n = 0, u_n = 0;
           const u32 np = min(jb & 3u, d.PG - 1u);
           for (u32 pg = 0; pg <= np && (jb >> 2) + pg < d.fp; ++pg) {  // (never beyond the node's fp cells)
-            const uint4 ch = ld4(d.obox[p.cur] + ((size_t)((jb >> 2) + pg) * d.Nl + l) * cu4 + 2u);
+            const uint4 ch = ld4(d.obox[p.fl.cur] + ((size_t)((jb >> 2) + pg) * d.Nl + l) * cu4 + 2u);
             const u32 hw[4] = {ch.x, ch.y, ch.z, ch.w};
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -127,12 +114,12 @@ __global__ __launch_bounds__(BLOCK) void traffic_send_kernel(Dev d, TrfDevP p) {
     pkts += n_p; recs += n_r; units += n_u;
   }
   // ---- the workgroup's column ----
-  trf_lds_sum(&acc[TRS_PKTS], pkts);
-  trf_lds_sum(&acc[TRS_RECS], recs);
-  trf_lds_sum(&acc[TRS_UNITS], units);
-  trf_lds_sum(&acc[TRS_SENDERS], senders);
-  trf_lds_max(&acc[TRS_PKT_RECS], prec);
-  trf_lds_max(&acc[TRS_PKT_UNITS], punits);
+  lds_sum(&acc[TRS_PKTS], pkts);
+  lds_sum(&acc[TRS_RECS], recs);
+  lds_sum(&acc[TRS_UNITS], units);
+  lds_sum(&acc[TRS_SENDERS], senders);
+  lds_max(&acc[TRS_PKT_RECS], prec);
+  lds_max(&acc[TRS_PKT_UNITS], punits);
   __syncthreads();
   if (threadIdx.x < TRS_REC + SIM_TRAFFIC_REC_BINS)
     p.part[(size_t)threadIdx.x * p.G + blockIdx.x] = threadIdx.x < TRS_REC ? (u64)acc[threadIdx.x] : (u64)bins[threadIdx.x - TRS_REC];
@@ -158,23 +145,7 @@ __global__ __launch_bounds__(BLOCK) void traffic_recv_kernel(Dev d, TickP ptp, T
       if (!fld) return;
       deg++; recs += fld & 31u; units += fld >> 5;
     };
-    if (d.rfan) {
-      const u32 b = p.rcsr[l], e = min(p.rcsr[l + 1], p.rcap);
-      for (u32 i = b; i < e; ++i) {
-        const u32 ent = p.rsrc[i];  // sender * 4 + slot
-        if ((ent >> 2) < d.Nl) take(ent >> 2, ent & 3u);
-      }
-    } else {
-      const u32 h = (u32)l / ptp.M, t = (u32)l - h * ptp.M;
-#pragma unroll
-      for (u32 k = 0; k < SIM_MAX_FANOUT; ++k) {
-        if (k >= p.nslot) continue;
-        u32 g, ll;
-        fan_source_g(ptp, PICK4(ptp.off, k), PICK4(ptp.rot, k), PICK4(ptp.rho, k), h, t, k, g, ll);
-        const u32 s = g * ptp.M + ll;
-        if (s < d.Nl) take(s, k);
-      }
-    }
+    recv_packets(d, ptp, p.fl, l, take);
     const bool up = d.R1[l].z & SIM_RF_UP;
     if (deg) {
       u32* m = p.map + l;
@@ -193,11 +164,11 @@ __global__ __launch_bounds__(BLOCK) void traffic_recv_kernel(Dev d, TickP ptp, T
     atomicAdd(&bins[min(deg, SIM_TRAFFIC_DEG_BINS - 1u)], 1u);  // (LDS)
   }
   // ---- the workgroup's column ----
-  trf_lds_sum(&acc[TRR_UP - TRR_UP], c_up);
-  trf_lds_sum(&acc[TRR_ADDRESSED - TRR_UP], c_addr);
-  trf_lds_sum(&acc[TRR_DOWN - TRR_UP], c_down);
-  trf_lds_max(&acc[TRR_MAXDEG - TRR_UP], kdeg);
-  trf_lds_max(&acc[TRR_MAXUNITS - TRR_UP], kunits);
+  lds_sum(&acc[TRR_UP - TRR_UP], c_up);
+  lds_sum(&acc[TRR_ADDRESSED - TRR_UP], c_addr);
+  lds_sum(&acc[TRR_DOWN - TRR_UP], c_down);
+  lds_max(&acc[TRR_MAXDEG - TRR_UP], kdeg);
+  lds_max(&acc[TRR_MAXUNITS - TRR_UP], kunits);
   __syncthreads();
   if (threadIdx.x < TRF_ROWS - TRR_UP)
     p.part[(size_t)(TRR_UP + threadIdx.x) * p.G + blockIdx.x] =
@@ -257,9 +228,9 @@ __global__ __launch_bounds__(BLOCK) void traffic_stat_kernel(u32 Nl, TrfStatP p)
     nz += v ? 1u : 0u;
     atomicAdd(&bins[min(v / p.bin_width, SIM_TRAFFIC_BINS - 1u)], 1u);  // (LDS)
   }
-  trf_lds_sum(&acc[TRT_SUM], sum);
-  trf_lds_max(&acc[TRT_MAX], key);
-  trf_lds_sum(&acc[TRT_NONZERO], nz);
+  lds_sum(&acc[TRT_SUM], sum);
+  lds_max(&acc[TRT_MAX], key);
+  lds_sum(&acc[TRT_NONZERO], nz);
   lo = wave_min(lo);
   if ((threadIdx.x & 63) == 0) atomicMin(&acc[TRT_MIN], (unsigned long long)lo);
   __syncthreads();
@@ -305,55 +276,14 @@ __global__ __launch_bounds__(BLOCK) void traffic_top_kernel(Dev d, TrfTopP p) {
   const bool up = in && (d.R1[in ? i : 0u].z & SIM_RF_UP);
   const u64 w[TRF_RANK_WORDS] = {(u64)i | ((u64)(up ? 1u : 0u) << 32), (u64)c[0] | ((u64)c[1] << 32), (u64)c[2] | ((u64)c[3] << 32),
                                  (u64)c[4] | ((u64)c[5] << 32), (u64)c[6] | ((u64)c[7] << 32)};
-  // the workgroup's candidates: round r takes the largest key below round r - 1's.  i < 2^24: a node's key is never 0
+  // i < 2^24: a node's key is never 0
   const u64 key = in ? ((u64)val << 32) | (u64)(0xFFFFFFFFu - i) : 0ull;
-  u64 prev = ~0ull;
-  u64* ck = p.ckey + (size_t)blockIdx.x * p.top_k;
-  u32 r = 0;
-  for (; r < p.top_k; ++r) {  // (the same in every lane)
-    const u64 m = roll_group_max(key < prev ? key : 0ull, red, r);
-    if (!m) break;
-    if (key == m) {
-      u64* dst = p.crec + ((size_t)blockIdx.x * p.top_k + r) * TRF_RANK_WORDS;
-      ck[r] = m;
-#pragma unroll
-      for (u32 k = 0; k < TRF_RANK_WORDS; ++k) dst[k] = w[k];
-    }
-    prev = m;
-  }
-  if (r < p.top_k && threadIdx.x == 0) ck[r] = 0;
+  rank_candidates<TRF_RANK_WORDS>(key, w, p.ckey, p.crec, p.top_k, red);
 }
-// one workgroup: the same selection over the workgroups' candidate lists (each sorted: the largest key of a list below the last one
-// chosen is the first below it); records beyond the nodes get id 0xFFFFFFFF and zeros
+// one workgroup: the lists merged; records beyond the nodes get id 0xFFFFFFFF and zeros
 __global__ __launch_bounds__(BLOCK) void traffic_top_fold(TrfTopP p) {
   __shared__ u64 red[2][BLOCK / 64];
-  u64 prev = ~0ull;
-  u32 r = 0;
-  for (; r < p.top_k; ++r) {  // (the same in every lane)
-    u64 best = 0;
-    size_t at = 0;
-    for (u32 g = threadIdx.x; g < p.G; g += BLOCK) {
-      const size_t base = (size_t)g * p.top_k;
-      for (u32 j = 0; j < p.top_k; ++j) {
-        const u64 k = p.ckey[base + j];
-        if (!k) break;
-        if (k < prev) {
-          if (k > best) { best = k; at = base + j; }
-          break;
-        }
-      }
-    }
-    const u64 m = roll_group_max(best, red, r);
-    if (!m) break;
-    if (best == m) {  // (keys are unique: one lane)
-      const u64* src = p.crec + at * TRF_RANK_WORDS;
-      u64* dst = p.top + (size_t)r * TRF_RANK_WORDS;
-#pragma unroll
-      for (u32 k = 0; k < TRF_RANK_WORDS; ++k) dst[k] = src[k];
-    }
-    prev = m;
-  }
-  for (u32 k = r * TRF_RANK_WORDS + threadIdx.x; k < p.top_k * TRF_RANK_WORDS; k += BLOCK) p.top[k] = k % TRF_RANK_WORDS ? 0ull : 0xFFFFFFFFull;
+  rank_merge<TRF_RANK_WORDS>(p.ckey, p.crec, p.G, p.top_k, p.top, red, FillNoId());
 }
 
 // ---- host ----
@@ -373,20 +303,11 @@ struct TrafficState : Observer {  // samples of 64 words
   }
   int sample(sim_handle* h, u64* out) override {
     const Dev& d = h->d;
-    const u64 t = h->tick - 1;  // the sampled tick: the one that sent the packets in flight
     TrfDevP p;
     p.psum = d_psum.get(); p.map = d_map.get(); p.part = d_part.get(); p.out = out;
-    p.rcsr = p.rsrc = nullptr;
-    p.rcap = 0;
-    if (d.rfan) {  // the rows of the packets sent during tick t, in front of the stream
-      if (int rc = rf_ready(h, t)) return rc;
-      p.rcsr = h->rf_rcsr[t % 3]; p.rsrc = h->rf_rsrc[t % 3];
-      p.rcap = d.f * d.Nl;
-    }
+    if (int rc = flight_fill(h, true, p.fl)) return rc;
     p.G = traffic_grid(h);
     p.now = (u32)h->tick;
-    p.cur = (u32)(h->tick & 1);
-    p.nslot = d.rfan ? d.f : h->prev.feff;  // (h->prev: the parameters of the tick that just ended, the one that sent the packets)
     p.samples = smp.taken + 1u;
     traffic_send_kernel<<<p.G, BLOCK, 0, h->stream>>>(d, p);
     traffic_recv_kernel<<<p.G, BLOCK, 0, h->stream>>>(d, h->prev, p);
@@ -422,7 +343,7 @@ int sim_traffic_nodes(sim_handle* h, uint32_t first_node, uint32_t count, sim_tr
   if (!s) return SIM_ESTATE;
   DevScratch<uint4> d_out;
   if (int rc = d_out.alloc((size_t)count * 2)) return rc;
-  int rc = spread_run(h, [&]() -> int {
+  int rc = observer_settle(h, [&]() -> int {
     if (!count) return SIM_OK;
     traffic_nodes_kernel<<<(count + BLOCK - 1) / BLOCK, BLOCK, 0, h->stream>>>(s->d_map.get(), h->d.Nl, first_node, count, d_out.get());
     HCHECK(hipGetLastError());
@@ -438,24 +359,16 @@ int sim_traffic_top(sim_handle* h, uint32_t top_k, uint32_t column, sim_traffic_
   if (!top || !top_k || top_k > SIM_TRAFFIC_TOP_MAX || column >= SIM_TRAFFIC_COLUMNS) return SIM_EINVAL;
   const TrafficState* s = traffic_of(h);
   if (!s) return SIM_ESTATE;
-  const size_t G = ((size_t)h->d.Nl + BLOCK - 1) / BLOCK;
-  DevScratch<u64> d_ckey, d_crec, d_top;
-  if (int rc = d_ckey.alloc(G * top_k)) return rc;
-  if (int rc = d_crec.alloc(G * top_k * TRF_RANK_WORDS)) return rc;
-  if (int rc = d_top.alloc((size_t)top_k * TRF_RANK_WORDS)) return rc;
-  int rc = spread_run(h, [&]() -> int {
+  return observer_read_top(h, top_k, 1u, TRF_RANK_WORDS, top, [&](u64* ckey, u64* crec, u64* d_top, u32 G) -> int {
     TrfTopP p;
-    p.map = s->d_map.get(); p.ckey = d_ckey.get(); p.crec = d_crec.get(); p.top = d_top.get();
-    p.G = (u32)G;
+    p.map = s->d_map.get(); p.ckey = ckey; p.crec = crec; p.top = d_top;
+    p.G = G;
     p.top_k = top_k; p.column = column;
     traffic_top_kernel<<<p.G, BLOCK, 0, h->stream>>>(h->d, p);
     traffic_top_fold<<<1, BLOCK, 0, h->stream>>>(p);
     HCHECK(hipGetLastError());
     return SIM_OK;
   });
-  if (rc != SIM_OK) return rc;
-  HCHECK(hipMemcpy(top, d_top.get(), (size_t)top_k * sizeof *top, hipMemcpyDeviceToHost));
-  return SIM_OK;
 }
 
 int sim_traffic_summary(sim_handle* h, uint32_t column, uint32_t bin_width, uint64_t* out) {
@@ -466,7 +379,7 @@ int sim_traffic_summary(sim_handle* h, uint32_t column, uint32_t bin_width, uint
   DevScratch<u64> part, d_out;
   if (int rc = part.alloc((size_t)TRT_ROWS * traffic_grid(h))) return rc;
   if (int rc = d_out.alloc(SIM_TRAFFIC_SUMMARY_WORDS)) return rc;
-  int rc = spread_run(h, [&]() -> int {
+  int rc = observer_settle(h, [&]() -> int {
     TrfStatP p;
     p.plane = s->d_map.get() + (size_t)column * h->d.Nl; p.part = part.get(); p.out = d_out.get();
     p.G = traffic_grid(h);

@@ -3,32 +3,30 @@
 // bookkeeping, the entry points.
 //
 // Per sampled tick, in stream order:
-//   tree_latch_kernel  a node per lane, grid-stride, TREE_GRID workgroups at most, whole waves kept together (the pass loop of
-//                      spread_latch_kernel).  The entries — uploaded at sim_tree_start as the ledger's table, index included — are staged once
-//                      per workgroup in LDS.  Per (node, entry): one coalesced 4-byte read of the arrival plane; the shared predicate
-//                      (spread_holds) only for a running node that has no arrival yet.  Where a node latches, its candidate — which lies in
+//   tree_latch_kernel  a node per lane, grid-stride, TREE_GRID workgroups at most, whole waves kept together.  The entries — uploaded at sim_tree_start as the ledger's table, index included — are staged once
+//                      per workgroup in LDS (lds_stage).  Per (node, entry): one coalesced 4-byte read of the arrival plane; the shared predicate
+//                      (rumour_held) only for a running node that has no arrival yet.  Where a node latches, its candidate — which lies in
 //                      the parent plane itself, scratch until now, valid when the node's bit of cmask[l] is set and the host says the
 //                      previous sample's stamp is now - 1 — is judged by its own arrival (a != 0 && a < now: a parent latching in this
 //                      launch reads as 0 or as now, and neither counts) and parent / hop are frozen.  have[l], a 64-bit mask of the
 //                      entries the node has an arrival for, is written whole, one coalesced 8-byte store
-//   tree_carry_kernel  the sender side, traffic_send_kernel's walk with ledger_count_kernel's match: all three uint4 of every page of every
-//                      DISTINCT packet the node sent, where they lie (obox[cur], 64- or 48-byte cells); a record's identity is looked up
-//                      in the LDS index.  One 64-bit carry mask per (slot, node) — a plane per slot —, copied to the slots that map to the
+//   tree_carry_kernel  the sender side (sent_packets, serf_sim_observe.inc): all three uint4 of every page of every DISTINCT packet the
+//                      node sent; a record's identity is looked up in the LDS index (ledger_find).  One 64-bit carry mask per (slot, node) — a plane per slot —, copied to the slots that map to the
 //                      same packet; `copies` through LDS adds, weighted by those slots (the ledger's word 6, counted the ledger's way)
-//   tree_cand_kernel   the receiver side, traffic_recv_kernel's walk: the graph rows of the sampled tick behind rf_ready under kRandomNodes,
-//                      fan_source_g under the bijection.  One 8-byte gather per packet, and-ed with ~have[l]; per set bit a minimum into the
+//   tree_cand_kernel   the receiver side (recv_packets; flight_fill puts the graph of the sampled tick in front of the stream under
+//                      kRandomNodes).  One 8-byte gather per packet, and-ed with ~have[l]; per set bit a minimum into the
 //                      node's own candidate — a lane owns its node: no race —; cmask[l] says which entries got one.  `fresh` through LDS adds
 //   tree_fold_kernel   one wave per word of the sample (fold_row).  `reached` and `orphans so far` are the previous sample's words plus
 //                      this sample's new ones: arrivals are written by samples only and the samples lie one behind the other
 // The count kernels write their workgroup's column of ONE partial matrix [1 + TREE_ROWS n][G] as 64-bit words — no atomics on global
 // memory, nothing to zero, every figure an integer, the result does not depend on order.  The planes are [n][Nl] uint32_t each, the
 // masks [Nl] / [4][Nl] uint64_t: every access of a wave to its own nodes is one contiguous run.
-// The reads (each behind a wait for the stream — spread_run —, on scratch of its own, the tree untouched):
+// The reads (each behind a wait for the stream — observer_settle —, on scratch of its own, the tree untouched):
 //   tree_children_kernel   children[parent[l]] += 1 on zeroed scratch: integer atomicAdd, the result does not depend on order
 //   tree_links_kernel      a slice of the three planes and the scratch transposed into 16-byte records
 //   tree_stat_kernel / tree_stat_fold   one entry's summary in one pass, its columns folded
 //   tree_path_kernel       one lane chases parent[] from the node to its orphan, hop + 1 ids
-//   tree_top_kernel / tree_top_fold     traffic_top_kernel's selection by (children << 32) | (0xFFFFFFFF - id)
+//   tree_top_kernel / tree_top_fold     the ranking in two levels (rank_candidates / rank_merge) by (children << 32) | (0xFFFFFFFF - id)
 // A handle without a started tree never gets here (sim_step_end finds its entry of the observers' table null).
 #include "../../include/serf_sim_tree.h"
 
@@ -62,28 +60,18 @@ struct TreeDevP {
   u64* part;          // [1 + TREE_ROWS n][G]
   u64* out;           // the sample's slot: 8 + 8 n words
   const u64* prev;    // the previous sample's slot; null: this is the first
-  const u32* rcsr;    // kRandomNodes: the graph of the sampled tick, [Nl + 1] / [rcap]
-  const u32* rsrc;
-  u32 rcap;
+  Flight fl;          // the packets of the sampled tick, its graph's rows included
   u32 G;              // workgroups of the per-tick kernels
   u32 n;              // entries
   u32 now;            // sim_tick after the sampled tick
-  u32 cur;            // parity of the cells that hold the packets in flight (obox[cur] / omap[cur])
-  u32 nslot;          // fan-out slots that carry packets: f (random fan-out), feff of the tick that sent them (bijection)
   u32 use_cand;       // the previous sample was taken and its stamp is now - 1
 };
-
-__device__ static inline void tree_stage(LedTab& tab, const LedTab* src_tab) {
-  const u32* src = reinterpret_cast<const u32*>(src_tab);
-  u32* dst = reinterpret_cast<u32*>(&tab);
-  for (u32 i = threadIdx.x; i < sizeof(LedTab) / 4; i += BLOCK) dst[i] = src[i];
-}
 
 __global__ __launch_bounds__(BLOCK) void tree_latch_kernel(Dev d, const uint4* base, TreeDevP p) {
   __shared__ LedTab tab;
   __shared__ u32 cnt[SIM_TREE_MAX * 2];  // new, new orphans
   __shared__ u32 s_up;
-  tree_stage(tab, p.tab);
+  lds_stage(tab, p.tab);
   for (u32 i = threadIdx.x; i < SIM_TREE_MAX * 2; i += BLOCK) cnt[i] = 0;
   if (threadIdx.x == 0) s_up = 0;
   __syncthreads();
@@ -102,7 +90,7 @@ __global__ __launch_bounds__(BLOCK) void tree_latch_kernel(Dev d, const uint4* b
       const size_t at = (size_t)e * d.Nl + l;
       u32 a = in ? p.arrival[at] : 0u;
       const u64 id = tab.id[e];
-      const bool latch = up && a == 0u && spread_holds(d, base, l, (u32)(id >> 32), (u32)id, tab.val[e]);
+      const bool latch = up && a == 0u && rumour_held(d, base, l, (u32)(id >> 32), (u32)id, tab.val[e]);
       bool orphan = false;
       if (latch) {
         u32 par = SIM_TREE_NONE, hp = 0;
@@ -132,55 +120,40 @@ __global__ __launch_bounds__(BLOCK) void tree_latch_kernel(Dev d, const uint4* b
 }
 
 __global__ __launch_bounds__(BLOCK) void tree_carry_kernel(Dev d, TreeDevP p) {
+  struct Sent {  // sent_packets' visitor: a packet's carry mask, copied to every slot that maps to it; `copies` weighs by those slots
+    const LedTab& tab;
+    u32* cnt;
+    u64 cm[SIM_MAX_FANOUT];  // (every index is a constant once the walk's loops are unrolled: registers)
+    __device__ void page(u32 k, u32 wgt, const uint4* cell) {
+      const uint4 ck = ld4(cell), cl = ld4(cell + 1), ch = ld4(cell + 2);
+      const u32 kw[4] = {ck.x, ck.y, ck.z, ck.w}, lw[4] = {cl.x, cl.y, cl.z, cl.w}, hw[4] = {ch.x, ch.y, ch.z, ch.w};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const u32 kind = SIM_META_KIND(hw[r]) & 7u;
+        if (!kind) continue;  // (an empty record is all zero)
+        const u32 e = ledger_find(tab, kind, kw[r], (u64)lw[r] | ((u64)(hw[r] >> 16) << 32));
+        if (e == LED_NONE) continue;
+        cm[k] |= 1ull << e;
+        atomicAdd(&cnt[e], wgt);  // (LDS)
+      }
+    }
+    __device__ void packet(u32, u32) {}
+    __device__ void repeat(u32 k, u32 first) { cm[k] = cm[first]; }
+  };
   __shared__ LedTab tab;
   __shared__ u32 cnt[SIM_TREE_MAX];  // copies
-  tree_stage(tab, p.tab);
+  lds_stage(tab, p.tab);
   if (threadIdx.x < SIM_TREE_MAX) cnt[threadIdx.x] = 0;
   __syncthreads();
   const size_t per_pass = (size_t)gridDim.x * BLOCK;
   const size_t passes = ((size_t)d.Nl + per_pass - 1) / per_pass;
-  const size_t cu4 = d.rfan ? RF_CELL_U4 : PK_U4;
   for (size_t it = 0; it < passes; ++it) {
     const size_t l = it * per_pass + (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (l >= d.Nl) continue;
-    const u32 jw = d.rfan ? d.obox[p.cur][l * RF_CELL_U4 + 3u].x : d.omap[p.cur][l];  // slot -> cell of the packets this node sent
-    u64 cm[SIM_MAX_FANOUT] = {0, 0, 0, 0};  // (every index below is a constant once the loops are unrolled: registers)
-    if (jw != 0xFFFFFFFFu) {
+    Sent v = {tab, cnt, {0, 0, 0, 0}};
+    sent_packets(d, p.fl.cur, p.fl.nslot, l, v);
 #pragma unroll
-      for (u32 k = 0; k < SIM_MAX_FANOUT; ++k) {
-        const u32 jb = (jw >> (8u * k)) & 0xFFu;  // first page << 2 | pages - 1
-        if (k >= p.nslot || jb == 0xFFu) continue;
-        bool again = false;
-        u32 wgt = 0;
-        u64 m = 0;
-#pragma unroll
-        for (u32 q = 0; q < SIM_MAX_FANOUT; ++q) {
-          const bool same = q < p.nslot && ((jw >> (8u * q)) & 0xFFu) == jb;
-          if (same && q < k) { again = true; m = cm[q]; }
-          wgt += same ? 1u : 0u;
-        }
-        if (!again) {  // a distinct packet is read once; it weighs as many slots as map to it
-          const u32 np = min(jb & 3u, d.PG - 1u);
-          for (u32 pg = 0; pg <= np && (jb >> 2) + pg < d.fp; ++pg) {  // (never beyond the node's fp cells)
-            const uint4* cell = d.obox[p.cur] + ((size_t)((jb >> 2) + pg) * d.Nl + l) * cu4;
-            const uint4 ck = ld4(cell), cl = ld4(cell + 1), ch = ld4(cell + 2);
-            const u32 kw[4] = {ck.x, ck.y, ck.z, ck.w}, lw[4] = {cl.x, cl.y, cl.z, cl.w}, hw[4] = {ch.x, ch.y, ch.z, ch.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const u32 kind = SIM_META_KIND(hw[r]) & 7u;
-              if (!kind) continue;  // (an empty record is all zero)
-              const u32 e = ledger_find(tab, kind, kw[r], (u64)lw[r] | ((u64)(hw[r] >> 16) << 32));
-              if (e == LED_NONE) continue;
-              m |= 1ull << e;
-              atomicAdd(&cnt[e], wgt);  // (LDS)
-            }
-          }
-        }
-        cm[k] = m;
-      }
-    }
-#pragma unroll
-    for (u32 k = 0; k < SIM_MAX_FANOUT; ++k) p.carry[(size_t)k * d.Nl + l] = cm[k];
+    for (u32 k = 0; k < SIM_MAX_FANOUT; ++k) p.carry[(size_t)k * d.Nl + l] = v.cm[k];
   }
   __syncthreads();
   for (u32 e = threadIdx.x; e < p.n; e += BLOCK) p.part[(size_t)(1u + e * TREE_ROWS + TRW_COPIES) * p.G + blockIdx.x] = cnt[e];
@@ -210,23 +183,7 @@ __global__ __launch_bounds__(BLOCK) void tree_cand_kernel(Dev d, TickP ptp, Tree
         if (up) atomicAdd(&cnt[e], 1u);  // (LDS)
       }
     };
-    if (d.rfan) {
-      const u32 b = p.rcsr[l], e = min(p.rcsr[l + 1], p.rcap);
-      for (u32 i = b; i < e; ++i) {
-        const u32 ent = p.rsrc[i];  // sender * 4 + slot
-        if ((ent >> 2) < d.Nl) take(ent >> 2, ent & 3u);
-      }
-    } else {
-      const u32 h = (u32)l / ptp.M, t = (u32)l - h * ptp.M;
-#pragma unroll
-      for (u32 k = 0; k < SIM_MAX_FANOUT; ++k) {
-        if (k >= p.nslot) continue;
-        u32 g, ll;
-        fan_source_g(ptp, PICK4(ptp.off, k), PICK4(ptp.rot, k), PICK4(ptp.rho, k), h, t, k, g, ll);
-        const u32 s = g * ptp.M + ll;
-        if (s < d.Nl) take(s, k);
-      }
-    }
+    recv_packets(d, ptp, p.fl, l, take);
     p.cmask[l] = seen;
   }
   __syncthreads();
@@ -298,11 +255,11 @@ __global__ __launch_bounds__(BLOCK) void tree_stat_kernel(u32 Nl, TreeStatP p) {
     atomicAdd(&bins[min(hp, SIM_TREE_BINS - 1u)], 1u);  // (LDS)
     atomicAdd(&bins[SIM_TREE_BINS + min(c, SIM_TREE_BINS - 1u)], 1u);
   }
-  trf_lds_sum(&acc[TRY_REACHED], reached);
-  trf_lds_sum(&acc[TRY_ORPHANS], orphans);
-  trf_lds_max(&acc[TRY_DEPTH], depth);
-  trf_lds_sum(&acc[TRY_HOPS], hops);
-  trf_lds_max(&acc[TRY_MOST], key);
+  lds_sum(&acc[TRY_REACHED], reached);
+  lds_sum(&acc[TRY_ORPHANS], orphans);
+  lds_max(&acc[TRY_DEPTH], depth);
+  lds_sum(&acc[TRY_HOPS], hops);
+  lds_max(&acc[TRY_MOST], key);
   __syncthreads();
   if (threadIdx.x < TRY_ROWS)
     p.part[(size_t)threadIdx.x * p.G + blockIdx.x] = threadIdx.x < TRY_BIN ? (u64)acc[threadIdx.x] : (u64)bins[threadIdx.x - TRY_BIN];
@@ -353,55 +310,14 @@ __global__ __launch_bounds__(BLOCK) void tree_top_kernel(Dev d, TreeTopP p) {
   const u32 par = a ? p.parent[i] : SIM_TREE_NONE, hp = a ? p.hop[i] : 0u, c = in ? p.ch[i] : 0u;
   const bool up = in && (d.R1[in ? i : 0u].z & SIM_RF_UP);
   const u64 w[TREE_RANK_WORDS] = {(u64)i | ((u64)(up ? 1u : 0u) << 32), (u64)a | ((u64)par << 32), (u64)hp | ((u64)c << 32)};
-  // the workgroup's candidates: round r takes the largest key below round r - 1's.  i < 2^24: a node's key is never 0
+  // i < 2^24: a node's key is never 0
   const u64 key = in ? ((u64)c << 32) | (u64)(0xFFFFFFFFu - i) : 0ull;
-  u64 prev = ~0ull;
-  u64* ck = p.ckey + (size_t)blockIdx.x * p.top_k;
-  u32 r = 0;
-  for (; r < p.top_k; ++r) {  // (the same in every lane)
-    const u64 m = roll_group_max(key < prev ? key : 0ull, red, r);
-    if (!m) break;
-    if (key == m) {
-      u64* dst = p.crec + ((size_t)blockIdx.x * p.top_k + r) * TREE_RANK_WORDS;
-      ck[r] = m;
-#pragma unroll
-      for (u32 k = 0; k < TREE_RANK_WORDS; ++k) dst[k] = w[k];
-    }
-    prev = m;
-  }
-  if (r < p.top_k && threadIdx.x == 0) ck[r] = 0;
+  rank_candidates<TREE_RANK_WORDS>(key, w, p.ckey, p.crec, p.top_k, red);
 }
-// one workgroup: the same selection over the workgroups' candidate lists (each sorted: the largest key of a list below the last one
-// chosen is the first below it); records beyond the nodes get id 0xFFFFFFFF and zeros
+// one workgroup: the lists merged; records beyond the nodes get id 0xFFFFFFFF and zeros
 __global__ __launch_bounds__(BLOCK) void tree_top_fold(TreeTopP p) {
   __shared__ u64 red[2][BLOCK / 64];
-  u64 prev = ~0ull;
-  u32 r = 0;
-  for (; r < p.top_k; ++r) {  // (the same in every lane)
-    u64 best = 0;
-    size_t at = 0;
-    for (u32 g = threadIdx.x; g < p.G; g += BLOCK) {
-      const size_t base = (size_t)g * p.top_k;
-      for (u32 j = 0; j < p.top_k; ++j) {
-        const u64 k = p.ckey[base + j];
-        if (!k) break;
-        if (k < prev) {
-          if (k > best) { best = k; at = base + j; }
-          break;
-        }
-      }
-    }
-    const u64 m = roll_group_max(best, red, r);
-    if (!m) break;
-    if (best == m) {  // (keys are unique: one lane)
-      const u64* src = p.crec + at * TREE_RANK_WORDS;
-      u64* dst = p.top + (size_t)r * TREE_RANK_WORDS;
-#pragma unroll
-      for (u32 k = 0; k < TREE_RANK_WORDS; ++k) dst[k] = src[k];
-    }
-    prev = m;
-  }
-  for (u32 k = r * TREE_RANK_WORDS + threadIdx.x; k < p.top_k * TREE_RANK_WORDS; k += BLOCK) p.top[k] = k % TREE_RANK_WORDS ? 0ull : 0xFFFFFFFFull;
+  rank_merge<TREE_RANK_WORDS>(p.ckey, p.crec, p.G, p.top_k, p.top, red, FillNoId());
 }
 
 // ---- host ----
@@ -445,25 +361,16 @@ struct TreeState : Observer {  // samples of 8 + 8 n words
   }
   int sample(sim_handle* h, u64* out) override {
     const Dev& d = h->d;
-    const u64 t = h->tick - 1;  // the sampled tick: the one that sent the packets in flight
     TreeDevP p;
     p.tab = d_tab.get();
     p.arrival = arrival(h); p.parent = parent(h); p.hop = hop(h);
     p.have = d_masks.get(); p.cmask = p.have + d.Nl; p.carry = p.have + (size_t)2 * d.Nl;
     p.part = d_part.get(); p.out = out;
     p.prev = smp.taken ? out - smp.stride_words : nullptr;
-    p.rcsr = p.rsrc = nullptr;
-    p.rcap = 0;
-    if (d.rfan) {  // the rows of the packets sent during tick t, in front of the stream
-      if (int rc = rf_ready(h, t)) return rc;
-      p.rcsr = h->rf_rcsr[t % 3]; p.rsrc = h->rf_rsrc[t % 3];
-      p.rcap = d.f * d.Nl;
-    }
+    if (int rc = flight_fill(h, true, p.fl)) return rc;
     p.G = tree_grid(h);
     p.n = n;
     p.now = (u32)h->tick;
-    p.cur = (u32)(h->tick & 1);
-    p.nslot = d.rfan ? d.f : h->prev.feff;  // (h->prev: the parameters of the tick that just ended, the one that sent the packets)
     p.use_cand = stamp + 1 == h->tick ? 1u : 0u;
     tree_latch_kernel<<<p.G, BLOCK, 0, h->stream>>>(d, h->d_base, p);
     tree_carry_kernel<<<p.G, BLOCK, 0, h->stream>>>(d, p);
@@ -518,7 +425,7 @@ int sim_tree_links(sim_handle* h, uint32_t entry, uint32_t first_node, uint32_t 
   DevScratch<uint4> d_out;
   if (int rc = d_ch.alloc(Nl)) return rc;
   if (int rc = d_out.alloc(count)) return rc;
-  int rc = spread_run(h, [&]() -> int {
+  int rc = observer_settle(h, [&]() -> int {
     if (!count) return SIM_OK;
     if (int lrc = tree_children_launch(h, s, entry, d_ch.get())) return lrc;
     tree_links_kernel<<<(count + BLOCK - 1) / BLOCK, BLOCK, 0, h->stream>>>(s->arrival(h) + entry * Nl, s->parent(h) + entry * Nl,
@@ -542,7 +449,7 @@ int sim_tree_summary(sim_handle* h, uint64_t* out) {
   if (int rc = d_ch.alloc(Nl)) return rc;
   if (int rc = part.alloc((size_t)TRY_ROWS * tree_grid(h))) return rc;
   if (int rc = d_out.alloc(words)) return rc;
-  int rc = spread_run(h, [&]() -> int {
+  int rc = observer_settle(h, [&]() -> int {
     for (u32 e = 0; e < s->n; ++e) {  // (the stream's order lets every entry use the same scratch)
       if (int lrc = tree_children_launch(h, s, e, d_ch.get())) return lrc;
       TreeStatP p;
@@ -568,23 +475,12 @@ int sim_tree_path(sim_handle* h, uint32_t entry, uint32_t node, uint32_t* ids, u
   if (!s) return SIM_ESTATE;
   if (entry >= s->n) return SIM_EINVAL;
   const size_t Nl = h->d.Nl;
-  const u32 room = std::min<u32>(cap, h->d.N);  // (no chain is longer than the nodes)
-  DevScratch<u32> d_ids;  // [room] ids, then the total
-  if (int rc = d_ids.alloc((size_t)room + 1)) return rc;
-  int rc = spread_run(h, [&]() -> int {
+  return observer_read_ids(h, ids, cap, n_out, total, [&](u32* d_ids, u32 room, u32*) -> int {  // (the kernel puts the total behind the ids)
     tree_path_kernel<<<1, 64, 0, h->stream>>>(s->arrival(h) + entry * Nl, s->parent(h) + entry * Nl, s->hop(h) + entry * Nl, (u32)Nl, node,
-                                              d_ids.get(), room);
+                                              d_ids, room);
     HCHECK(hipGetLastError());
     return SIM_OK;
   });
-  if (rc != SIM_OK) return rc;
-  u32 tot = 0;
-  HCHECK(hipMemcpy(&tot, d_ids.get() + room, 4, hipMemcpyDeviceToHost));
-  const u32 got = std::min(tot, room);
-  if (got) HCHECK(hipMemcpy(ids, d_ids.get(), (size_t)got * 4, hipMemcpyDeviceToHost));
-  *n_out = got;
-  *total = tot;
-  return SIM_OK;
 }
 
 int sim_tree_top(sim_handle* h, uint32_t entry, uint32_t top_k, sim_tree_rank* ranks) {
@@ -593,28 +489,21 @@ int sim_tree_top(sim_handle* h, uint32_t entry, uint32_t top_k, sim_tree_rank* r
   const TreeState* s = tree_of(h);
   if (!s) return SIM_ESTATE;
   if (entry >= s->n) return SIM_EINVAL;
-  const size_t Nl = h->d.Nl, G = (Nl + BLOCK - 1) / BLOCK;
+  const size_t Nl = h->d.Nl;
   DevScratch<u32> d_ch;
-  DevScratch<u64> d_ckey, d_crec, d_top;
   if (int rc = d_ch.alloc(Nl)) return rc;
-  if (int rc = d_ckey.alloc(G * top_k)) return rc;
-  if (int rc = d_crec.alloc(G * top_k * TREE_RANK_WORDS)) return rc;
-  if (int rc = d_top.alloc((size_t)top_k * TREE_RANK_WORDS)) return rc;
-  int rc = spread_run(h, [&]() -> int {
+  return observer_read_top(h, top_k, 1u, TREE_RANK_WORDS, ranks, [&](u64* ckey, u64* crec, u64* d_top, u32 G) -> int {
     if (int lrc = tree_children_launch(h, s, entry, d_ch.get())) return lrc;
     TreeTopP p;
     p.arrival = s->arrival(h) + entry * Nl; p.parent = s->parent(h) + entry * Nl; p.hop = s->hop(h) + entry * Nl; p.ch = d_ch.get();
-    p.ckey = d_ckey.get(); p.crec = d_crec.get(); p.top = d_top.get();
-    p.G = (u32)G;
+    p.ckey = ckey; p.crec = crec; p.top = d_top;
+    p.G = G;
     p.top_k = top_k;
     tree_top_kernel<<<p.G, BLOCK, 0, h->stream>>>(h->d, p);
     tree_top_fold<<<1, BLOCK, 0, h->stream>>>(p);
     HCHECK(hipGetLastError());
     return SIM_OK;
   });
-  if (rc != SIM_OK) return rc;
-  HCHECK(hipMemcpy(ranks, d_top.get(), (size_t)top_k * sizeof *ranks, hipMemcpyDeviceToHost));
-  return SIM_OK;
 }
 
 }  // extern "C"
