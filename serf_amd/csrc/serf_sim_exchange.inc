@@ -172,6 +172,70 @@ int sim_t_self_direct(sim_handle* h, int on) {
   h->self_direct = on != 0;
   return SIM_OK;
 }
+// Test hook (SIM_CF_RANDOM_FANOUT; exported, not declared in the header): the fan-out graph of ANY tick, through the handle's own
+// launch path — rf_build with its RfP, its choice of instantiation and its scratch — after both streams have drained; buffer
+// tick % 3 then holds that tick's graph and rf_q says so: rf_ready / rf_look_ahead build again whatever the tick needs.
+//   which = 0  what the handle builds.  One handle: rcsr[Nl + 1] | rsrc[rcsr[Nl]].  A shard (the sending side), per sender
+//              chunk: rsrc[f * Nl / C] | cntb[N] bytes, padded to a word | btot[NB] | xoff[2 V + 2].
+//   which = 1  a shard's receiving side as the last sim_step_begin left it, nothing is built: rx_rcsr[Nl + 1] | rx_rsrc[rx_rcsr[Nl]].
+// Returns the words written (SIM_ERANGE: more than cap_words).  info: 0 LB, 1 PB, 2 NB, 3 NBh, 4 cap, 5 bcap, 6 wide entries,
+// 7 lean rf_rows, 8 NWG, the slab's 9 cnt_u, 10 tot_u, 11 cell_u, 12 slab_u, 13 cap (0 on one handle), and of the build just
+// run (a shard: of its last chunk): 14 the largest bucket total, 15 the entries on the overflow list.
+int sim_t_rf_graph(sim_handle* h, uint64_t tick, uint32_t which, uint32_t* out, size_t cap_words, uint32_t* info) {
+  if (!h || !h->d.rfan || !out || !info || which > 1u || (which == 1u && !h->d.sharded) || h->in_tick) return SIM_EINVAL;
+  const Dev& d = h->d;
+  const RfP& r = h->rfp;
+  const u32 C = d.sharded ? h->rf_C : 1u, spw = h->rf_wide ? RfSpw<u64>::v : RfSpw<u32>::v;
+  const u32 set[14] = {r.LB, r.PB, r.NB, r.NBh, r.cap, r.bcap, h->rf_wide ? 1u : 0u, rf_lean(r) ? 1u : 0u, (d.Nl / C + spw - 1u) / spw,
+                       d.sharded ? h->rfx.cnt_u : 0u, d.sharded ? h->rfx.tot_u : 0u, d.sharded ? h->rfx.cell_u : 0u,
+                       d.sharded ? h->rfx.slab_u : 0u, d.sharded ? h->rfx.cap : 0u};
+  memcpy(info, set, sizeof set);
+  info[14] = info[15] = 0;
+  HCHECK(hipStreamSynchronize(h->rf_stream));
+  HCHECK(hipStreamSynchronize(h->stream));
+  size_t at = 0;
+  auto take = [&](const void* src, size_t words) -> int {  // `words` words of device memory -> out[at ..]
+    if (at + words > cap_words) return SIM_ERANGE;
+    if (words && hipMemcpy(out + at, src, words * 4u, hipMemcpyDeviceToHost) != hipSuccess) return SIM_EDEVICE;
+    at += words;
+    return SIM_OK;
+  };
+  if (which == 1u) {
+    if (int rc = take(h->rx_rcsr, (size_t)d.Nl + 1u)) return rc;
+    if (int rc = take(h->rx_rsrc, std::min<u32>(out[d.Nl], h->rx_cap))) return rc;
+    return (int)at;
+  }
+  if (int rc = rf_build(h, tick, h->stream)) return rc;
+  // (rf_done[tick % 3] is not recorded: both streams were drained above and this build is waited for below, so whatever that event
+  // last marked — or nothing — has completed and rf_ready's hipEventQuery on it succeeds without a wait)
+  h->rf_q[tick % 3] = tick;
+  HCHECK(hipStreamSynchronize(h->stream));
+  {  // the counters of the parity the (last) build used: the next build zeroes them
+    const u32 par = h->rf_par ^ 1u;
+    std::vector<u32> g((size_t)r.NB * RF_GCS);
+    HCHECK(hipMemcpy(g.data(), h->rf_gcur[par], g.size() * 4u, hipMemcpyDeviceToHost));
+    for (u32 b = 0; b < r.NB; ++b) info[14] = std::max(info[14], g[(size_t)b * RF_GCS]);
+    HCHECK(hipMemcpy(&info[15], h->rf_ovf[par], 4u, hipMemcpyDeviceToHost));
+  }
+  const u32 i = (u32)(tick % 3);
+  if (!d.sharded) {
+    if (int rc = take(h->rf_rcsr[i], (size_t)d.Nl + 1u)) return rc;
+    if (int rc = take(h->rf_rsrc[i], std::min<u32>(out[d.Nl], r.rcap))) return rc;
+    return (int)at;
+  }
+  const size_t per = (size_t)d.f * (d.Nl / C);
+  for (u32 c = 0; c < C; ++c) {
+    const size_t cw = ((size_t)d.N + 3u) / 4u;
+    if (int rc = take(h->rf_rsrc[i] + c * per, per)) return rc;
+    if (at + cw > cap_words) return SIM_ERANGE;
+    out[at + cw - 1u] = 0;  // (the padding of the count bytes)
+    if (hipMemcpy(out + at, h->rf_cntb[i] + (size_t)c * d.N, d.N, hipMemcpyDeviceToHost) != hipSuccess) return SIM_EDEVICE;
+    at += cw;
+    if (int rc = take(h->rf_btot[i] + (size_t)c * r.NB, r.NB)) return rc;
+    if (int rc = take(h->rf_xoff[i] + (size_t)c * (2u * d.V + 2u), 2u * (size_t)d.V + 2u)) return rc;
+  }
+  return (int)at;
+}
 // Test hook (host arithmetic only, no device): the fan-out map of `tick` for global node `gid` — its targets and the
 // nodes whose packets land on it, both through the general forms the support kernels use.  Returns feff.
 int sim_t_fanmap(const sim_config* cfg, uint64_t tick, uint32_t gid, uint32_t* targets, uint32_t* sources) {

@@ -180,6 +180,8 @@ static int create_rf(sim_handle* h);
 static int sreq_take(sim_handle* h, u64 t, uint32_t* out, uint32_t cap_pairs, uint32_t* n_pairs);
 static int rfx_pack(sim_handle* h, u64 t, u32 c);
 static int rf_reset(sim_handle* h);
+static int rf_build(sim_handle* h, u64 tick, hipStream_t s);  // (the test hook sim_t_rf_graph, serf_sim_exchange.inc)
+static bool rf_lean(const RfP& r);
 static hipEvent_t tick_done_event(const sim_handle* h, u64 t);
 
 #define HCHECK(x)                                                                        \

@@ -95,6 +95,7 @@ static int create_rf(sim_handle* h) {
     ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
   return ok ? SIM_OK : SIM_EDEVICE;
 }
+static bool rf_lean(const RfP& r) { return r.cap <= 11u * RFR && (1u << r.LB) <= 2u * RFR; }  // rf_rows' lean instantiation: 11 pairs and 2 rows per thread are enough
 // the fan-out graph of `tick`, on stream `s`: rf_rcsr / rf_rsrc [tick % 3] := the rows of the packets sent during `tick` (E: the entry type)
 template <typename E>
 static int rf_build_as(sim_handle* h, u64 tick, hipStream_t s) {
@@ -108,7 +109,7 @@ static int rf_build_as(sim_handle* h, u64 tick, hipStream_t s) {
   r.Ns = h->d.Nl / C;
   r.rcap = h->d.f * r.Ns;
   r.NWG = (u32)(((size_t)r.Ns + RfSpw<E>::v - 1u) / RfSpw<E>::v);
-  const bool lean = r.cap <= 11u * RFR && (1u << r.LB) <= 2u * RFR;  // rf_rows' lean instantiation: 11 pairs and 2 rows per thread are enough
+  const bool lean = rf_lean(r);
   for (u32 c = 0; c < C; ++c) {
     r.lfirst = c * r.Ns;
     u32 *rcsr = h->rf_rcsr[tick % 3], *rsrc = h->rf_rsrc[tick % 3] + (size_t)c * r.rcap;
