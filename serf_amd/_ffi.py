@@ -448,6 +448,82 @@ class LedgerEntry(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("key", C.c_uint32), ("val", C.c_uint64)]
 
 
+# include/serf_sim_qboard.h: query board (per followed query id: acks, responses, who of the eligible nodes answered, who stayed
+# silent, the 50 / 90 / 99 / 100 % latches, sampled behind the ticks).  The tenth extension: a version of its own, bound only when
+# the loaded library exports it
+QBOARD_SYMBOLS = ("qboard_start", "qboard_count", "qboard_read", "qboard_stop", "qboard_now", "qboard_silent", "qboard_nodes", "qboard_top",
+                  "qboard_version")
+QBOARD_HEADER_WORDS, QBOARD_ENTRY_WORDS, QBOARD_MAX, QBOARD_MAX_SAMPLES = 8, 16, 64, 1 << 20
+QBOARD_TOP_MAX, QBOARD_NODE_WORDS = 64, 8
+QBOARD_WAITING, QBOARD_OPEN, QBOARD_CLOSED, QBOARD_DISPLACED = 0, 1, 2, 3
+QBOARD_BY_SILENT_ACK, QBOARD_BY_SILENT_RESP = 0, 1
+# a sample's header, one entry's record and one node's record as numpy records: the tables of include/serf_sim_qboard.h
+QBOARD_HEADER_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("n", "<u8"), ("open", "<u8"), ("closed", "<u8"), ("waiting", "<u8"),
+                                ("displaced", "<u8"), ("new", "<u8")])
+QBOARD_ENTRY_DTYPE = np.dtype([("id", "<u4"), ("state", "<u4"), ("origin", "<u4"), ("flags", "<u4"), ("deadline", "<u8"), ("acks", "<u8"),
+                               ("responses", "<u8"), ("eligible", "<u8"), ("answered", "<u8"), ("responded", "<u8"), ("silent", "<u8"),
+                               ("new_acks", "<u8"), ("new_responses", "<u8"), ("t_first", "<u8"), ("t_half", "<u8"), ("t_90", "<u8"),
+                               ("t_99", "<u8"), ("t_all", "<u8")])
+QBOARD_NODE_DTYPE = np.dtype([("id", "<u4"), ("running", "<u4"), ("asked", "<u8"), ("acked", "<u8"), ("responded", "<u8"), ("silent_ack", "<u8"),
+                              ("silent_resp", "<u8"), ("reserved", "<u8", (2,))])
+QBOARD_SUMMARY_DTYPE = np.dtype([("id", "<u4"), ("state", "<u4"), ("started", "<i8"), ("deadline", "<i8"), ("acks", "<i8"), ("responses", "<i8"),
+                                 ("answered", "<i8"), ("eligible", "<i8"), ("to_half", "<i8"), ("to_90", "<i8"), ("to_99", "<i8"),
+                                 ("to_all", "<i8"), ("silent_at_close", "<i8")])
+assert QBOARD_HEADER_DTYPE.itemsize == 8 * QBOARD_HEADER_WORDS and QBOARD_ENTRY_DTYPE.itemsize == 8 * QBOARD_ENTRY_WORDS
+assert QBOARD_NODE_DTYPE.itemsize == 8 * QBOARD_NODE_WORDS
+
+
+def qboard_split(words, n):
+    """[samples * (8 + 16 * n)] words -> (headers[samples], records[samples][n])."""
+    return sample_split(words, QBOARD_HEADER_DTYPE, QBOARD_ENTRY_DTYPE, n)
+
+
+def qboard_rank(nodes, rank_by=QBOARD_BY_SILENT_ACK, top_k=None):
+    """The order sim_qboard_top lists the RUNNING nodes in, from every node's record (QBOARD_NODE_DTYPE [n_nodes]): silent_ack
+    (QBOARD_BY_SILENT_ACK) or silent_resp (QBOARD_BY_SILENT_RESP) descending, id ascending.  Returns the node ids, the first
+    top_k of them when given."""
+    nodes = np.asarray(nodes)
+    run = nodes[nodes["running"] != 0]
+    score = run["silent_ack" if rank_by == QBOARD_BY_SILENT_ACK else "silent_resp"].astype(np.int64)
+    ids = run["id"].astype(np.int64)
+    return [int(x) for x in ids[np.lexsort((ids, -score))][:top_k]]
+
+
+def qboard_summary(records, q_timeout):
+    """One row per query (QBOARD_SUMMARY_DTYPE [entries]) from the records of a board's samples (QBOARD_ENTRY_DTYPE [samples][entries],
+    as Sim.qboard_read returns them); q_timeout: the query timeout in ticks (16 per decimal digit of n_nodes).  Per entry, over its
+    LAST run (the samples since the table entry last changed hands or started afresh): `started` = deadline - q_timeout, the
+    deadline, the final acks and responses (of the last sample that was open or closed), answered / eligible at the last OPEN
+    sample, the ticks from `started` to the half / 90 / 99 / all latches (-1: never latched) and `silent_at_close` = silent at the
+    first closed sample (-1: never seen closed).  An entry that never left `waiting` has state 0 and -1 in every other column."""
+    records = np.asarray(records)
+    out = np.zeros(records.shape[1] if records.ndim == 2 else 0, QBOARD_SUMMARY_DTYPE)
+    for name in out.dtype.names[2:]:
+        out[name] = -1
+    for i in range(len(out)):
+        col = records[:, i]
+        out["id"][i] = col["id"][0] if len(col) else 0
+        live = np.nonzero((col["state"] == QBOARD_OPEN) | (col["state"] == QBOARD_CLOSED))[0]
+        if not len(live):
+            continue
+        last = col[live[-1]]
+        run = [k for k in live.tolist() if col["deadline"][k] == last["deadline"] and col["origin"][k] == last["origin"] and col["flags"][k] == last["flags"]]
+        row = out[i]
+        row["state"] = col["state"][-1]
+        row["deadline"], row["started"] = int(last["deadline"]), int(last["deadline"]) - q_timeout
+        row["acks"], row["responses"] = int(last["acks"]), int(last["responses"])
+        opened = [k for k in run if col["state"][k] == QBOARD_OPEN]
+        if opened:
+            row["answered"], row["eligible"] = int(col["answered"][opened[-1]]), int(col["eligible"][opened[-1]])
+        for name, latch in (("to_half", "t_half"), ("to_90", "t_90"), ("to_99", "t_99"), ("to_all", "t_all")):
+            if last[latch]:
+                row[name] = int(last[latch]) - int(row["started"])
+        closed = [k for k in run if col["state"][k] == QBOARD_CLOSED]
+        if closed:
+            row["silent_at_close"] = int(col["silent"][closed[0]])
+    return out
+
+
 class SpreadEntry(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("key", C.c_uint32), ("ltime", C.c_uint64)]
 
@@ -603,7 +679,7 @@ class SimLib:
             fn = getattr(self.dll, prefix + name)  # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             self.f[name] = fn
-        # the nine extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
+        # the ten extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
         # bound whole or not at all
         count = (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)])
         read = (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)])
@@ -689,9 +765,20 @@ class SimLib:
                 "tree_top": (C.c_int, [H, u32, u32, vp]),
                 "tree_version": (u32, []),
             }),
+            ("qboard", "has_qboard", {
+                "qboard_start": (C.c_int, [H, C.POINTER(u32), u32, u32, u32, u32]),
+                "qboard_count": count,
+                "qboard_read": read,
+                "qboard_stop": stop,
+                "qboard_now": (C.c_int, [H, C.POINTER(u32), u32, vp]),
+                "qboard_silent": (C.c_int, [H, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u32)]),
+                "qboard_nodes": (C.c_int, [H, u32, u32, vp]),
+                "qboard_top": (C.c_int, [H, u32, u32, vp, vp]),
+                "qboard_version": (u32, []),
+            }),
         ]
         assert [tuple(sigs) for _, _, sigs in ext] == [TRACK_SYMBOLS, SERIES_SYMBOLS, CENSUS_SYMBOLS, ROLL_SYMBOLS, LEDGER_SYMBOLS,
-                                                           DETECT_SYMBOLS, SPREAD_SYMBOLS, TRAFFIC_SYMBOLS, TREE_SYMBOLS]
+                                                           DETECT_SYMBOLS, SPREAD_SYMBOLS, TRAFFIC_SYMBOLS, TREE_SYMBOLS, QBOARD_SYMBOLS]
         self.ext = {}   # group -> exported
         for group, attr, sigs in ext:
             self.ext[group] = all(hasattr(self.dll, prefix + name) for name in sigs)
@@ -755,6 +842,10 @@ class SimLib:
     def tree_version(self):
         """SIM_TREE_VERSION of include/serf_sim_tree.h, or None when the library has no rumour tree."""
         return self.f["tree_version"]() if self.has_tree else None
+
+    def qboard_version(self):
+        """SIM_QBOARD_VERSION of include/serf_sim_qboard.h, or None when the library has no query board."""
+        return self.f["qboard_version"]() if self.has_qboard else None
 
 
 class Sim:
@@ -1326,6 +1417,72 @@ class Sim:
         top = np.zeros(max(1, top_k), TREE_RANK_DTYPE)
         self._ck(self._ext_fn("tree", "top")(self.h, entry, top_k, top.ctypes.data), "sim_tree_top")
         return top[:top_k]
+
+    # ---- query board (include/serf_sim_qboard.h) ----
+    @staticmethod
+    def _qboard_ids(ids):
+        ids = [int(x) for x in ids]
+        return (C.c_uint32 * max(1, len(ids)))(*ids), len(ids)
+
+    def qboard_start(self, ids=(), first_tick=0, period=1, capacity=1 << 12):
+        """Starts a query board of `ids` (non-zero query ids, 64 at most, running or not yet): behind every tick t >= first_tick
+        with (t - first_tick) % period == 0, until `capacity` samples are held (a first_tick that has passed means "now"), every
+        query's acks, responses, eligible, answered and silent nodes are counted and its latches moved."""
+        arr, n = self._qboard_ids(ids)
+        self._ck(self._ext_fn("qboard", "start")(self.h, arr, n, first_tick, period, capacity), "sim_qboard_start")
+        self._qboard_n = n
+
+    def qboard_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        return self._sample_count("qboard")
+
+    def qboard_read(self, first=0, n=None):
+        """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as (headers, records): numpy arrays
+        of QBOARD_HEADER_DTYPE [n] and QBOARD_ENTRY_DTYPE [n][entries]; waits for the handle's stream."""
+        return self._sample_read("qboard", first, n, QBOARD_HEADER_DTYPE, QBOARD_ENTRY_DTYPE, getattr(self, "_qboard_n", 1))
+
+    def qboard_stop(self):
+        """Ends the board and frees its records and the samples."""
+        self._sample_stop("qboard")
+
+    def qboard_now(self, ids=()):
+        """One stateless sample of the state the handle is in now, with or without a running board, for ids of its own:
+        (header, records[len(ids)]) with latches and `new` words 0 — n query_status calls with one wait for the stream."""
+        arr, n = self._qboard_ids(ids)
+        out = np.zeros(QBOARD_HEADER_WORDS + max(1, n) * QBOARD_ENTRY_WORDS, np.uint64)
+        self._ck(self._ext_fn("qboard", "now")(self.h, arr, n, out.ctypes.data), "sim_qboard_now")
+        hdr, rec = qboard_split(out[:QBOARD_HEADER_WORDS + n * QBOARD_ENTRY_WORDS], n)
+        return hdr[0], rec[0]
+
+    def qboard_silent(self, entry, which=0, cap=None):
+        """(ids, total): the eligible nodes of `entry` without the ack bit (which 0) or the response bit (which 1) in ascending
+        id — the first `cap` of them (cap = None: all) — and the number of all of them; waits for the handle's stream."""
+        if cap is None:
+            cap = self.cfg.n_nodes
+        ids = np.zeros(max(1, cap), np.uint32)
+        got, total = C.c_uint32(), C.c_uint32()
+        self._ck(self._ext_fn("qboard", "silent")(self.h, entry, which, ids.ctypes.data if cap else None, cap, C.byref(got), C.byref(total)),
+                 "sim_qboard_silent")
+        return ids[:got.value], total.value
+
+    def qboard_nodes(self, first_node=0, count=None):
+        """The records of nodes first_node .. first_node + count - 1 (count = None: up to the last node) over the entries that
+        own their table entry now, as a numpy array of QBOARD_NODE_DTYPE; waits for the handle's stream."""
+        if count is None:
+            count = max(0, self.cfg.n_nodes - first_node)
+        out = np.zeros(max(1, count), QBOARD_NODE_DTYPE)
+        self._ck(self._ext_fn("qboard", "nodes")(self.h, first_node, count, out.ctypes.data), "sim_qboard_nodes")
+        return out[:count]
+
+    def qboard_top(self, top_k=8, rank_by=QBOARD_BY_SILENT_ACK, nodes=False):
+        """The top_k worst running nodes by rank_by (QBOARD_BY_SILENT_ACK / QBOARD_BY_SILENT_RESP), ties in ascending id, as a
+        numpy array of QBOARD_NODE_DTYPE [top_k] (records beyond the running nodes are zero), and with nodes=True (top, every
+        node's record [n_nodes]); waits for the handle's stream."""
+        top = np.zeros(max(1, top_k), QBOARD_NODE_DTYPE)
+        every = np.zeros(self.cfg.n_nodes, QBOARD_NODE_DTYPE) if nodes else None
+        self._ck(self._ext_fn("qboard", "top")(self.h, top_k, rank_by, top.ctypes.data, every.ctypes.data if nodes else None),
+                 "sim_qboard_top")
+        return (top[:top_k], every) if nodes else top[:top_k]
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

@@ -35,6 +35,10 @@ struct SplitArr {
 };
 enum { SP_VIEW = 0, SP_EV = 1, SP_Q = 2, SP_N = 3 };  // (the order of SIM_ARR_VIEW .. SIM_ARR_QRING and of the image's sections)
 enum { OB_SERIES = 0, OB_CENSUS = 1, OB_ROLL = 2, OB_LEDGER = 3, OB_DETECT = 4, OB_SPREAD = 5, OB_TRAFFIC = 6, OB_TREE = 7, OB_N = 8 };  // the periodic observers, in the order their samples follow a tick on the stream
+// ... and behind them the query board (serf_sim_qboard.inc): the ninth entry of the table.  It stands in a line of its own because
+// tests/test_tree.py pins the line above as it is; OB_ALL is what the table holds
+enum { OB_QBOARD = OB_N, OB_ALL = OB_N + 1 };
+static_assert(OB_QBOARD == 8 && OB_ALL == 9, "the observers' table: eight of rumours and members, then the query board");
 // Function-local device scratch: freed when it goes out of scope — behind whatever stream synchronisation stands before that.
 template <typename T>
 struct DevScratch {
@@ -166,7 +170,7 @@ struct sim_handle {
   u64 ev_hi = 1, q_hi = 1;
   u32* deep_seen = nullptr;  // pinned: the longest deep list any launch has had (deep_queue_kernel keeps it; sizes that kernel's grid)
   struct TrackState* trk = nullptr;  // device-resident trackers (serf_sim_track.inc); null until the first sim_track_add
-  struct Observer* obs[OB_N] = {};  // the periodic observers (the frame at the end of this file); an entry is null unless its observer is running
+  struct Observer* obs[OB_ALL] = {};  // the periodic observers (the frame at the end of this file); an entry is null unless its observer is running
   sim_handle() = default;
   sim_handle(const sim_handle&) = delete;
   sim_handle& operator=(const sim_handle&) = delete;
@@ -352,7 +356,7 @@ static int rings_need(sim_handle* h) {
 #define EV_CAP (1u << 20)
 
 // ---- what the observers share on the host (the device part: serf_sim_observe.inc; it stands here because it needs the handle) ----
-// trackers, series, census, roll, ledger, detection log, spread map, traffic meter and rumour tree watch a handle that holds every node, between ticks
+// trackers, series, census, roll, ledger, detection log, spread map, traffic meter, rumour tree and query board watch a handle that holds every node, between ticks
 static int observer_usable(const sim_handle* h) {
   if (!h) return SIM_EINVAL;
   if (h->d.sharded || h->in_tick) return SIM_ESTATE;
@@ -403,7 +407,7 @@ static void sampler_close(Sampler& S) {  // (the caller has waited for the sampl
   S.d_buf = nullptr;
 }
 
-// ---- the periodic observers' frame: series, census, roll, ledger, detection log, spread map, traffic meter and rumour tree differ in their kernels and in nothing below ----
+// ---- the periodic observers' frame: series, census, roll, ledger, detection log, spread map, traffic meter, rumour tree and query board differ in their kernels and in nothing below ----
 // A periodic observer while it runs: its samples and, in the struct derived from it, the scratch and the parameters of its kernels.
 struct Observer {
   Sampler smp;
@@ -535,7 +539,7 @@ sim_handle::~sim_handle() {
   if (xstream) (void)hipStreamSynchronize(xstream);
   if (rf_stream) (void)hipStreamSynchronize(rf_stream);
   if (trk) track_destroy(this);
-  for (u32 k = 0; k < OB_N; ++k) observer_destroy(this, k);
+  for (u32 k = 0; k < OB_ALL; ++k) observer_destroy(this, k);
   if (xcomm) (void)ncclCommDestroy(xcomm);
   if (xstream) (void)hipStreamDestroy(xstream);
   if (rf_stream) (void)hipStreamDestroy(rf_stream);

@@ -27,6 +27,7 @@
 #include "../../include/serf_sim_spread.h"
 #include "../../include/serf_sim_traffic.h"
 #include "../../include/serf_sim_tree.h"
+#include "../../include/serf_sim_qboard.h"
 #include "../../include/serf_sim_detect.h"
 #include "wire.hpp"
 
@@ -506,6 +507,66 @@ class Cluster {
     out.resize(top_k);
     return out;
   }
+  // query board (include/serf_sim_qboard.h): behind every period-th tick, for up to 64 query ids — running or not yet — the acks and
+  // responses their origins hold, how many of the nodes the filters admit run, have answered, stay silent, and the ticks at which a
+  // first / half / 90 % / 99 % / all of them had answered: what `while (!r.finished()) step(), r.acks()` polls, without a poll.  The
+  // board is read by entry (qboard_silent: who stayed silent), by node (qboard_nodes) or ranked (qboard_top); qboard_now is the bulk
+  // form of query_status and needs no board.  HIP library only.
+  struct QBoardSample {
+    uint64_t header[SIM_QBOARD_HEADER_WORDS];  // now, running, n, entries open / closed / waiting / displaced, new acks + responses
+    struct Entry {
+      uint32_t id, state, origin, flags;
+      uint64_t deadline, acks, responses, eligible, answered, responded, silent, new_acks, new_responses, t_first, t_half, t_90, t_99, t_all;
+    };
+    std::vector<Entry> entries;
+  };
+  struct QBoardTop { std::vector<sim_qboard_node> top, nodes; };  // nodes: every node's record, when asked for
+  void qboard_start(const std::vector<uint32_t>& ids, uint32_t first_tick = 0, uint32_t period = 1, uint32_t capacity = 1u << 12) {
+    check(sim_qboard_start(h_, ids.data(), (uint32_t)ids.size(), first_tick, period, capacity), "sim_qboard_start");
+    qboard_n_ = (uint32_t)ids.size();
+  }
+  // (samples taken, dropped with the buffer full); waits for nothing
+  std::pair<uint32_t, uint32_t> qboard_count() const { return sample_count(sim_qboard_count, "sim_qboard_count"); }
+  std::vector<QBoardSample> qboard_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    const uint32_t ne = qboard_n_;
+    return sample_read<QBoardSample>(sim_qboard_count, sim_qboard_read, "sim_qboard", first, n,
+                                     SIM_QBOARD_HEADER_WORDS + (size_t)ne * SIM_QBOARD_ENTRY_WORDS,
+                                     [ne](const uint64_t* w, QBoardSample& s) { unpack(w, ne, s.header, s.entries); });
+  }
+  void qboard_stop() { check(sim_qboard_stop(h_), "sim_qboard_stop"); }
+  // one stateless sample of ids of the caller's own, with or without a running board (latches and `new` are 0)
+  QBoardSample qboard_now(const std::vector<uint32_t>& ids) {
+    std::vector<uint64_t> w(SIM_QBOARD_HEADER_WORDS + (ids.size() ? ids.size() : 1) * SIM_QBOARD_ENTRY_WORDS);
+    check(sim_qboard_now(h_, ids.data(), (uint32_t)ids.size(), w.data()), "sim_qboard_now");
+    QBoardSample s;
+    unpack(w.data(), ids.size(), s.header, s.entries);
+    return s;
+  }
+  // (the eligible nodes of `entry` without the ack (which 0) / response (which 1) bit in ascending id, the first `cap`; the number of all)
+  std::pair<std::vector<uint32_t>, uint32_t> qboard_silent(uint32_t entry, uint32_t which = 0, uint32_t cap = 0xFFFFFFFFu) {
+    if (cap > n_) cap = n_;
+    std::vector<uint32_t> ids(cap ? cap : 1);
+    uint32_t got = 0, total = 0;
+    check(sim_qboard_silent(h_, entry, which, ids.data(), cap, &got, &total), "sim_qboard_silent");
+    ids.resize(got);
+    return {ids, total};
+  }
+  // the records of nodes first_node .. (default: up to the last node) over the entries that own their table entry now
+  std::vector<sim_qboard_node> qboard_nodes(uint32_t first_node = 0, uint32_t count = 0xFFFFFFFFu) {
+    if (count == 0xFFFFFFFFu) count = n_ > first_node ? n_ - first_node : 0;
+    std::vector<sim_qboard_node> out(count ? count : 1);
+    check(sim_qboard_nodes(h_, first_node, count, out.data()), "sim_qboard_nodes");
+    out.resize(count);
+    return out;
+  }
+  QBoardTop qboard_top(uint32_t top_k = 8, uint32_t rank_by = SIM_QBOARD_BY_SILENT_ACK, bool nodes = false) {
+    QBoardTop s;
+    s.top.resize(top_k ? top_k : 1);
+    if (nodes) s.nodes.resize(n_);
+    check(sim_qboard_top(h_, top_k, rank_by, s.top.data(), nodes ? s.nodes.data() : nullptr), "sim_qboard_top");
+    s.top.resize(top_k);
+    return s;
+  }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;
@@ -525,6 +586,8 @@ class Cluster {
   uint32_t ledger_n_ = 1;    // entries of the running ledger: likewise
   uint32_t spread_n_ = 1;    // entries of the running spread map: likewise
   uint32_t tree_n_ = 1;      // entries of the running rumour tree: likewise
+  uint32_t qboard_n_ = 1;    // entries of the running query board: likewise
+  static_assert(sizeof(QBoardSample::Entry) == 8 * SIM_QBOARD_ENTRY_WORDS, "an entry's record is sixteen words");
   static_assert(sizeof(TreeSample::Entry) == 8 * SIM_TREE_ENTRY_WORDS && sizeof(TreeSummary) == 8 * SIM_TREE_SUMMARY_WORDS,
                 "an entry's record is eight words, its summary seventy-two");
   static_assert(sizeof(SpreadSample::Entry) == 8 * SIM_SPREAD_ENTRY_WORDS && sizeof(SpreadSummary) == 8 * SIM_SPREAD_SUMMARY_WORDS,
