@@ -2,7 +2,9 @@
 
 Each test names the reference test it restates (paths under /root/reference/serf-core/src).  String
 ids of the reference ("test", "foo", ...) become small integer node ids; node 0 plays `s1`.
-These pin the oracle: tests/test_parity_gpu.py then pins the HIP path to the oracle.
+These pin the oracle: tests/test_parity_gpu.py then pins the HIP path to the oracle.  The arms are also replayed ON THE GPU, through the
+tick kernel's receive path: tests/delivery_table.py restates them as records in flight towards prepared nodes (its `kat/` cases, each
+naming its test here), tests/test_delivery_table.py holds them to the literal answers, tests/test_delivery_table_gpu.py delivers them.
 """
 import ctypes as C
 
