@@ -524,6 +524,53 @@ def qboard_summary(records, q_timeout):
     return out
 
 
+# include/serf_sim_catalog.h: rumour catalogue (the live record identities FOUND behind the ticks, not named in advance, and a
+# registry of every identity ever found).  The eleventh extension: a version of its own, bound only when the loaded library
+# exports it
+CATALOG_SYMBOLS = ("catalog_start", "catalog_count", "catalog_read", "catalog_stop", "catalog_list", "catalog_live", "catalog_now",
+                   "catalog_version")
+CATALOG_LIVE, CATALOG_MAX, CATALOG_MAX_SAMPLES, CATALOG_SAMPLE_WORDS, CATALOG_RECORD_WORDS, CATALOG_KINDS = 256, 4096, 1 << 20, 48, 8, 0xFE
+# a sample, a live identity (the ledger's entry layout) and a registry record as numpy records: the tables of
+# include/serf_sim_catalog.h.  by-kind columns: index 0 is kind 1
+CATALOG_SAMPLE_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("live", "<u8"), ("overflow", "<u8"), ("new", "<u8"), ("died", "<u8"),
+                                 ("revived", "<u8"), ("registry", "<u8"), ("ids_lost", "<u8"), ("queued", "<u8"), ("in_flight", "<u8"),
+                                 ("packets", "<u8"), ("transmits", "<u8"), ("live_by_kind", "<u8", (7,)), ("queued_by_kind", "<u8", (7,)),
+                                 ("in_flight_by_kind", "<u8", (7,)), ("overflowed", "<u8"), ("reserved", "<u8", (13,))])
+CATALOG_LIVE_DTYPE = np.dtype([("id", "<u8"), ("val", "<u8"), ("reserved", "<u8"), ("holders", "<u8"), ("queued", "<u8"),
+                               ("transmits", "<u8"), ("in_flight", "<u8"), ("fresh", "<u8")])
+CATALOG_RECORD_DTYPE = np.dtype([("id", "<u8"), ("val", "<u8"), ("first_seen", "<u4"), ("last_seen", "<u4"), ("samples", "<u4"),
+                                 ("revivals", "<u4"), ("peak_queued", "<u4"), ("peak_queued_at", "<u4"), ("peak_holders", "<u4"),
+                                 ("peak_holders_at", "<u4"), ("in_flight_sum", "<u8"), ("queued_sum", "<u8")])
+assert CATALOG_SAMPLE_DTYPE.itemsize == 8 * CATALOG_SAMPLE_WORDS
+assert CATALOG_LIVE_DTYPE.itemsize == CATALOG_RECORD_DTYPE.itemsize == 8 * CATALOG_RECORD_WORDS
+
+
+def catalog_mask(kinds):
+    """Kinds (1-7) -> kinds_mask: bit k set means kind k is catalogued."""
+    m = 0
+    for k in kinds:
+        m |= 1 << int(k)
+    return m
+
+
+def catalog_summary(records):
+    """What a catalogue's registry (CATALOG_RECORD_DTYPE, as Sim.catalog_list returns it) says, as a dict: `identities` — one
+    dict per record, in the registry's order, with kind, key, val and the record's fields —, and `by_kind`: kind -> how many
+    identities the registry holds of it, the copies sent for them (in_flight_sum) and the longest life in ticks."""
+    records = np.asarray(records)
+    ids, by_kind = [], {}
+    for r in records:
+        kind, key = int(r["id"]) >> 32, int(r["id"]) & 0xFFFFFFFF
+        d = dict(kind=kind, key=key, val=int(r["val"]))
+        d.update({n: int(r[n]) for n in CATALOG_RECORD_DTYPE.names[2:]})
+        ids.append(d)
+        k = by_kind.setdefault(kind, dict(identities=0, copies=0, longest_life=0))
+        k["identities"] += 1
+        k["copies"] += d["in_flight_sum"]
+        k["longest_life"] = max(k["longest_life"], d["last_seen"] - d["first_seen"] + 1)
+    return dict(identities=ids, by_kind=dict(sorted(by_kind.items())))
+
+
 class SpreadEntry(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("key", C.c_uint32), ("ltime", C.c_uint64)]
 
@@ -679,7 +726,7 @@ class SimLib:
             fn = getattr(self.dll, prefix + name)  # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             self.f[name] = fn
-        # the ten extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
+        # the eleven extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
         # bound whole or not at all
         count = (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)])
         read = (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)])
@@ -776,9 +823,20 @@ class SimLib:
                 "qboard_top": (C.c_int, [H, u32, u32, vp, vp]),
                 "qboard_version": (u32, []),
             }),
+            ("catalog", "has_catalog", {
+                "catalog_start": (C.c_int, [H, u32, u32, u32, u32, u32]),
+                "catalog_count": count,
+                "catalog_read": read,
+                "catalog_stop": stop,
+                "catalog_list": (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]),
+                "catalog_live": (C.c_int, [H, vp, C.c_size_t, C.POINTER(u32)]),
+                "catalog_now": (C.c_int, [H, u32, vp, vp, C.c_size_t, C.POINTER(u32)]),
+                "catalog_version": (u32, []),
+            }),
         ]
         assert [tuple(sigs) for _, _, sigs in ext] == [TRACK_SYMBOLS, SERIES_SYMBOLS, CENSUS_SYMBOLS, ROLL_SYMBOLS, LEDGER_SYMBOLS,
-                                                           DETECT_SYMBOLS, SPREAD_SYMBOLS, TRAFFIC_SYMBOLS, TREE_SYMBOLS, QBOARD_SYMBOLS]
+                                                           DETECT_SYMBOLS, SPREAD_SYMBOLS, TRAFFIC_SYMBOLS, TREE_SYMBOLS, QBOARD_SYMBOLS,
+                                                           CATALOG_SYMBOLS]
         self.ext = {}   # group -> exported
         for group, attr, sigs in ext:
             self.ext[group] = all(hasattr(self.dll, prefix + name) for name in sigs)
@@ -846,6 +904,10 @@ class SimLib:
     def qboard_version(self):
         """SIM_QBOARD_VERSION of include/serf_sim_qboard.h, or None when the library has no query board."""
         return self.f["qboard_version"]() if self.has_qboard else None
+
+    def catalog_version(self):
+        """SIM_CATALOG_VERSION of include/serf_sim_catalog.h, or None when the library has no rumour catalogue."""
+        return self.f["catalog_version"]() if self.has_catalog else None
 
 
 class Sim:
@@ -1483,6 +1545,61 @@ class Sim:
         self._ck(self._ext_fn("qboard", "top")(self.h, top_k, rank_by, top.ctypes.data, every.ctypes.data if nodes else None),
                  "sim_qboard_top")
         return (top[:top_k], every) if nodes else top[:top_k]
+
+    # ---- rumour catalogue (include/serf_sim_catalog.h) ----
+    def catalog_start(self, kinds_mask=CATALOG_KINDS, max_ids=CATALOG_MAX, first_tick=0, period=1, capacity=1 << 12):
+        """Starts a catalogue of the kinds in kinds_mask (bit k: kind k; catalog_mask) with a registry of max_ids records: behind
+        every tick t >= first_tick with (t - first_tick) % period == 0, until `capacity` samples are held (a first_tick that has
+        passed means "now"), the live record identities are found, counted and entered into the registry."""
+        self._ck(self._ext_fn("catalog", "start")(self.h, kinds_mask, max_ids, first_tick, period, capacity), "sim_catalog_start")
+
+    def catalog_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        return self._sample_count("catalog")
+
+    def catalog_read(self, first=0, n=None):
+        """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as a numpy array of
+        CATALOG_SAMPLE_DTYPE; waits for the handle's stream."""
+        fn = self._ext_fn("catalog", "read")
+        if n is None:
+            n = max(0, self._sample_count("catalog")[0] - first)
+        out = np.zeros(max(1, n), CATALOG_SAMPLE_DTYPE)
+        got = C.c_uint32()
+        self._ck(fn(self.h, first, n, out.ctypes.data, max(1, n) * CATALOG_SAMPLE_WORDS, C.byref(got)), "sim_catalog_read")
+        return out[:got.value]
+
+    def catalog_stop(self):
+        """Ends the catalogue and frees the samples and the registry."""
+        self._sample_stop("catalog")
+
+    def catalog_list(self, first=0, n=None):
+        """Registry records first .. first + n - 1 (n = None: up to the last) as a numpy array of CATALOG_RECORD_DTYPE, in the
+        registry's fixed order; waits for the handle's stream."""
+        if n is None:
+            n = CATALOG_MAX
+        out = np.zeros(max(1, n), CATALOG_RECORD_DTYPE)
+        got, total = C.c_uint32(), C.c_uint32()
+        self._ck(self._ext_fn("catalog", "list")(self.h, first, n, out.ctypes.data, max(1, n) * CATALOG_RECORD_WORDS, C.byref(got),
+                                                   C.byref(total)), "sim_catalog_list")
+        return out[:got.value]
+
+    def catalog_live(self):
+        """The live table of the latest sample taken as a numpy array of CATALOG_LIVE_DTYPE in ascending (id, val) — empty before
+        the first sample and after an overflowed one; waits for the handle's stream."""
+        out = np.zeros(CATALOG_LIVE, CATALOG_LIVE_DTYPE)
+        got = C.c_uint32()
+        self._ck(self._ext_fn("catalog", "live")(self.h, out.ctypes.data, CATALOG_LIVE * 8, C.byref(got)), "sim_catalog_live")
+        return out[:got.value]
+
+    def catalog_now(self, kinds_mask=CATALOG_KINDS):
+        """One scan of the state the handle is in now, with or without a running catalogue, which it does not touch:
+        (sample, live table) as CATALOG_SAMPLE_DTYPE and CATALOG_LIVE_DTYPE [live]; it has no registry: the sample's words
+        4-8 and 34 are 0."""
+        hdr, out = np.zeros(1, CATALOG_SAMPLE_DTYPE), np.zeros(CATALOG_LIVE, CATALOG_LIVE_DTYPE)
+        got = C.c_uint32()
+        self._ck(self._ext_fn("catalog", "now")(self.h, kinds_mask, hdr.ctypes.data, out.ctypes.data, CATALOG_LIVE * 8, C.byref(got)),
+                 "sim_catalog_now")
+        return hdr[0], out[:got.value]
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

@@ -60,7 +60,7 @@ typedef uint64_t u64;
 // every suspicion timer can fire (dead) and the probe can fail (suspect): Dev::npend = fanout * pkt_records + SIM_S + 1
 
 
-// One translation unit, seventeen files (r5: the 5 700-line file, split where its sections ended).  It stays ONE unit on purpose: the
+// One translation unit, eighteen files (r5: the 5 700-line file, split where its sections ended).  It stays ONE unit on purpose: the
 // handlers are force-inlined into the tick kernel across these files — separate device translation units would need relocatable
 // device code, which changes the code the compiler generates for the hot kernel — and the host side launches the kernel
 // templates it instantiates.  bench.py stamps its PMC profiles with the hash of the DEVICE files (state, handlers, tick).
@@ -89,3 +89,4 @@ extern "C" {
 #include "serf_sim_traffic.inc"  // include/serf_sim_traffic.h: likewise
 #include "serf_sim_tree.inc"  // include/serf_sim_tree.h: likewise
 #include "serf_sim_qboard.inc"  // include/serf_sim_qboard.h: likewise
+#include "serf_sim_catalog.inc"  // include/serf_sim_catalog.h: likewise

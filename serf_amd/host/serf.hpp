@@ -28,6 +28,7 @@
 #include "../../include/serf_sim_traffic.h"
 #include "../../include/serf_sim_tree.h"
 #include "../../include/serf_sim_qboard.h"
+#include "../../include/serf_sim_catalog.h"
 #include "../../include/serf_sim_detect.h"
 #include "wire.hpp"
 
@@ -567,6 +568,55 @@ class Cluster {
     s.top.resize(top_k);
     return s;
   }
+  // rumour catalogue (include/serf_sim_catalog.h): behind every period-th tick the record identities that are LIVE — queued at a
+  // running node or in a packet in flight — are found, not named: a sample of 48 words, the live table of the latest sample and a
+  // registry of every identity ever found (first and last seen, peaks, the copies it cost).  Feed what it lists to the ledger, the
+  // spread map or the tree.
+  struct CatalogSample { uint64_t w[SIM_CATALOG_SAMPLE_WORDS]; };  // the words of the header's table
+  struct CatalogLive { uint64_t id, val, reserved, holders, queued, transmits, in_flight, fresh; };  // the ledger's entry layout
+  struct CatalogRecord {
+    uint64_t id, val;
+    uint32_t first_seen, last_seen, samples, revivals, peak_queued, peak_queued_at, peak_holders, peak_holders_at;
+    uint64_t in_flight_sum, queued_sum;
+    uint32_t kind() const { return (uint32_t)(id >> 32); }
+    uint32_t key() const { return (uint32_t)id; }
+  };
+  struct CatalogNow { CatalogSample sample; std::vector<CatalogLive> live; };
+  void catalog_start(uint32_t kinds_mask = SIM_CATALOG_KINDS, uint32_t max_ids = SIM_CATALOG_MAX, uint32_t first_tick = 0, uint32_t period = 1,
+                     uint32_t capacity = 1u << 12) {
+    check(sim_catalog_start(h_, kinds_mask, max_ids, first_tick, period, capacity), "sim_catalog_start");
+  }
+  std::pair<uint32_t, uint32_t> catalog_count() const { return sample_count(sim_catalog_count, "sim_catalog_count"); }
+  std::vector<CatalogSample> catalog_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    return sample_read<CatalogSample>(sim_catalog_count, sim_catalog_read, "sim_catalog", first, n, SIM_CATALOG_SAMPLE_WORDS,
+                                      [](const uint64_t* w, CatalogSample& s) { std::memcpy(s.w, w, sizeof s.w); });
+  }
+  void catalog_stop() { check(sim_catalog_stop(h_), "sim_catalog_stop"); }
+  // registry records first .. first + n - 1 (default: up to the last), in the registry's fixed order
+  std::vector<CatalogRecord> catalog_list(uint32_t first = 0, uint32_t n = SIM_CATALOG_MAX) {
+    std::vector<CatalogRecord> out(n ? n : 1);
+    uint32_t got = 0, total = 0;
+    check(sim_catalog_list(h_, first, n, reinterpret_cast<uint64_t*>(out.data()), out.size() * SIM_CATALOG_RECORD_WORDS, &got, &total), "sim_catalog_list");
+    out.resize(got);
+    return out;
+  }
+  // the live table of the latest sample, ascending (id, val); empty before the first sample and after an overflowed one
+  std::vector<CatalogLive> catalog_live() {
+    std::vector<CatalogLive> out(SIM_CATALOG_LIVE);
+    uint32_t got = 0;
+    check(sim_catalog_live(h_, reinterpret_cast<uint64_t*>(out.data()), out.size() * 8, &got), "sim_catalog_live");
+    out.resize(got);
+    return out;
+  }
+  // one scan of the state the handle is in now, with or without a running catalogue, which it does not touch
+  CatalogNow catalog_now(uint32_t kinds_mask = SIM_CATALOG_KINDS) {
+    CatalogNow s;
+    s.live.resize(SIM_CATALOG_LIVE);
+    uint32_t got = 0;
+    check(sim_catalog_now(h_, kinds_mask, s.sample.w, reinterpret_cast<uint64_t*>(s.live.data()), s.live.size() * 8, &got), "sim_catalog_now");
+    s.live.resize(got);
+    return s;
+  }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;
@@ -588,6 +638,8 @@ class Cluster {
   uint32_t tree_n_ = 1;      // entries of the running rumour tree: likewise
   uint32_t qboard_n_ = 1;    // entries of the running query board: likewise
   static_assert(sizeof(QBoardSample::Entry) == 8 * SIM_QBOARD_ENTRY_WORDS, "an entry's record is sixteen words");
+  static_assert(sizeof(CatalogLive) == 64 && sizeof(CatalogRecord) == 8 * SIM_CATALOG_RECORD_WORDS && sizeof(CatalogSample) == 8 * SIM_CATALOG_SAMPLE_WORDS,
+                "a live identity and a registry record are eight words, a sample forty-eight");
   static_assert(sizeof(TreeSample::Entry) == 8 * SIM_TREE_ENTRY_WORDS && sizeof(TreeSummary) == 8 * SIM_TREE_SUMMARY_WORDS,
                 "an entry's record is eight words, its summary seventy-two");
   static_assert(sizeof(SpreadSample::Entry) == 8 * SIM_SPREAD_ENTRY_WORDS && sizeof(SpreadSummary) == 8 * SIM_SPREAD_SUMMARY_WORDS,

@@ -288,6 +288,28 @@ def detect_json(args, sim):
             "last_header": None if hdr is None else {name: (hdr[name].tolist() if hdr[name].ndim else int(hdr[name])) for name in hdr.dtype.names}}
 
 
+def catalog_json(args, sim):
+    """The run's rumour catalogue: what the registry holds by kind (_ffi.catalog_summary), the identities nobody named — every
+    record that is not one of the tool's own user events — and the live curve."""
+    from serf_amd import _ffi
+    taken, dropped = sim.catalog_count()
+    s, reg = sim.catalog_read(), sim.catalog_list()
+    summ = _ffi.catalog_summary(reg)
+    unnamed = [d for d in summ["identities"] if not (d["kind"] == _ffi.K_EVENT and d["key"] >> 24 == 0x40)]
+    by_kind = {}
+    for d in unnamed:
+        by_kind[d["kind"]] = by_kind.get(d["kind"], 0) + 1
+    sim.catalog_stop()
+    return {"period": args.catalog, "samples": taken, "dropped": dropped,
+            "what": "include/serf_sim_catalog.h: the record identities found live behind the sampled ticks; by_kind: kind -> identities "
+                    "in the registry, copies sent for them (period 1), longest life in ticks; unnamed_by_kind: those that are not the "
+                    "tool's own user events",
+            "registry": len(reg), "ids_lost": int(s["ids_lost"][-1]) if len(s) else 0, "overflowed_samples": int(s["overflowed"][-1]) if len(s) else 0,
+            "by_kind": {str(k): v for k, v in summ["by_kind"].items()}, "unnamed_by_kind": {str(k): v for k, v in sorted(by_kind.items())},
+            "live_max": int(s["live"].max()) if len(s) else 0, "live_by_kind_max": s["live_by_kind"].max(axis=0).tolist() if len(s) else [],
+            "tick": s["tick"].tolist(), "live": s["live"].tolist(), "new": s["new"].tolist(), "died": s["died"].tolist()}
+
+
 def traffic_json(args, sim):
     """The run's traffic meter: per-node byte rates, the hottest receivers, what went to stopped processes, the in-degree histogram."""
     from serf_amd import _ffi
@@ -421,6 +443,7 @@ def run_tracker(args, sim, lib):
     tree = tree.json() if tree else None
     detect = detect_json(args, sim) if args.detect else None
     traffic = traffic_json(args, sim) if args.traffic else None
+    catalog = catalog_json(args, sim) if args.catalog else None
 
     def rounds(name):
         return [r[name] - t for t, r in done_ev if r[name] != NEVER]
@@ -460,6 +483,8 @@ def run_tracker(args, sim, lib):
         out["detect"] = detect
     if traffic:
         out["traffic"] = traffic
+    if catalog:
+        out["catalog"] = catalog
     json.dump(out, open(args.out, "w"), indent=None if series or census or roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "sim_step_calls", "crashes", "events", "false_positives", "model_bound_drops", "ops_dropped_no_slot", "wall_s")}), "->", args.out)
     print(json.dumps({"rounds_to_99": out["rounds_to"]["99"], "detection": out["detection"]}))
@@ -504,6 +529,7 @@ def main():
     ap.add_argument("--detect", type=int, default=0, metavar="PERIOD", help="judge every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_detect.h): the episodes of every crash and every accusation of the run, their summary into the JSON")
     ap.add_argument("--tree", action="store_true", help="--tracker: follow the first 64 user events with rumour trees, latched behind every tick (include/serf_sim_tree.h), and put their hop histograms, depths, orphans and the ten nodes with the most children into the JSON")
     ap.add_argument("--traffic", type=int, default=0, metavar="PERIOD", help="meter the gossip packets per sender and per target on the device behind every PERIOD-th tick (include/serf_sim_traffic.h): per-node byte percentiles and the ten hottest receivers into the JSON")
+    ap.add_argument("--catalog", type=int, default=0, metavar="PERIOD", help="find the live record identities on the device behind every PERIOD-th tick (include/serf_sim_catalog.h): the registry by kind, the identities nobody named and the live curve into the JSON")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.ledger and not args.tracker:
@@ -513,7 +539,7 @@ def main():
     if args.tree and not args.tracker:
         ap.error("--tree follows the rumours of a --tracker run")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r15_config4_tree.json" if args.tree else "r14_config4_traffic.json" if args.traffic else "r12_config4_detect.json" if args.detect else "r13_config4_spread.json" if args.spread else "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
+        args.out = os.path.join(ROOT, "profiles", "r17_config4_catalog.json" if args.catalog else "r15_config4_tree.json" if args.tree else "r14_config4_traffic.json" if args.traffic else "r12_config4_detect.json" if args.detect else "r13_config4_spread.json" if args.spread else "r11_config4_ledger.json" if args.ledger else "r10_config4_roll.json" if args.roll else "r09_config4_census.json" if args.census else "r08_config4_series.json" if args.series else "r07_config4_tracker.json" if args.tracker else "r03_config4_churn5_loss1_swim.json")
 
     import numpy as np
     from serf_amd import _ffi
@@ -543,6 +569,8 @@ def main():
         sim.detect_start(0, args.detect, min(_ffi.DETECT_MAX_SAMPLES, 1 << 16), 1 << 20)
     if args.traffic:
         sim.traffic_start(0, args.traffic, min(_ffi.TRAFFIC_MAX_SAMPLES, 1 << 16))
+    if args.catalog:
+        sim.catalog_start(_ffi.CATALOG_KINDS, _ffi.CATALOG_MAX, 0, args.catalog, min(_ffi.CATALOG_MAX_SAMPLES, 1 << 16))
     if args.tracker:
         return run_tracker(args, sim, lib)
     rng = np.random.default_rng(5)
@@ -598,7 +626,7 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect", "spread", "traffic", "tree")},
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect", "spread", "traffic", "tree", "catalog")},
         "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
@@ -631,6 +659,8 @@ def main():
         out["detect"] = detect_json(args, sim)
     if args.traffic:
         out["traffic"] = traffic_json(args, sim)
+    if args.catalog:
+        out["catalog"] = catalog_json(args, sim)
     json.dump(out, open(args.out, "w"), indent=None if args.series or args.census or args.roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "churn_events", "rounds_to_99", "model_bound_drops", "ops_dropped_no_slot", "failure_detector", "wall_s")}), "->", args.out)
 
