@@ -571,6 +571,45 @@ def catalog_summary(records):
     return dict(identities=ids, by_kind=dict(sorted(by_kind.items())))
 
 
+# include/serf_sim_gazette.h: member gazette (every node's member events — Join / Leave / Failed / Reap, flaps — by view
+# diffs behind the ticks, per node and per subject).  The twelfth extension: a version of its own, bound only when the
+# loaded library exports it
+GAZETTE_SYMBOLS = ("gazette_start", "gazette_count", "gazette_read", "gazette_nodes", "gazette_subjects", "gazette_top", "gazette_stop",
+                   "gazette_version")
+GAZETTE_WORDS, GAZETTE_COLS, GAZETTE_TOP_MAX, GAZETTE_MAX_SAMPLES = 64, 8, 64, 1 << 20
+GAZETTE_MAP_NODES, GAZETTE_MAP_SUBJECTS = 0, 1
+GAZETTE_COLUMNS = ("join", "leave", "failed", "reap", "flap", "suspected", "cleared", "peak")
+GAZETTE_JOIN, GAZETTE_LEAVE, GAZETTE_FAILED, GAZETTE_REAP, GAZETTE_FLAP, GAZETTE_SUSPECTED, GAZETTE_CLEARED, GAZETTE_PEAK = range(8)
+# a sample and a place of a ranking as numpy records: the tables of include/serf_sim_gazette.h
+GAZETTE_SAMPLE_DTYPE = np.dtype([("tick", "<u8"), ("running", "<u8"), ("slots", "<u8"), ("fresh", "<u8"), ("matrix", "<u8", (5, 5)),
+                                 ("swim", "<u8", (4, 4)), ("sums", "<u8", (7,)), ("nodes", "<u8"), ("node_max", "<u8"), ("node_id", "<u8"),
+                                 ("subjects", "<u8"), ("subject_id", "<u8"), ("subject_max", "<u8"), ("dead_time", "<u8", (5,)),
+                                 ("reserved", "<u8")])
+GAZETTE_RANK_DTYPE = np.dtype([("id", "<u8"), ("row", "<u4", (8,))])
+assert GAZETTE_SAMPLE_DTYPE.itemsize == 8 * GAZETTE_WORDS and GAZETTE_RANK_DTYPE.itemsize == 40
+
+
+def gazette_rates(samples, nodes=None):
+    """What a gazette's samples (GAZETTE_SAMPLE_DTYPE, as Sim.gazette_read returns them) say, as a dict: the ticks they span,
+    per column 0-6 the total and the events per tick — serf.member.join / leave / flap among them —, and with `nodes` (the
+    node map, as Sim.gazette_nodes returns it) the median, the 99th percentile and the maximum of the events of columns 0-3 a
+    node saw."""
+    samples = np.asarray(samples)
+    out = dict(samples=int(len(samples)), ticks=0, totals={}, per_tick={})
+    if len(samples):
+        out["ticks"] = int(samples["tick"][-1]) - int(samples["tick"][0]) + 1
+    sums = samples["sums"].astype(np.int64).sum(axis=0) if len(samples) else np.zeros(7, np.int64)
+    for k, name in enumerate(GAZETTE_COLUMNS[:7]):
+        out["totals"][name] = int(sums[k])
+        out["per_tick"][name] = float(sums[k]) / out["ticks"] if out["ticks"] else 0.0
+    if nodes is not None:
+        ev = np.asarray(nodes)[:, :4].astype(np.int64).sum(axis=1)
+        srt = np.sort(ev)
+        pick = lambda q: int(srt[min(len(srt) - 1, int(np.ceil(q * len(srt))) - 1)]) if len(srt) else 0     # nearest rank
+        out["per_node"] = dict(median=pick(0.5), p99=pick(0.99), max=int(srt[-1]) if len(srt) else 0)
+    return out
+
+
 class SpreadEntry(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("key", C.c_uint32), ("ltime", C.c_uint64)]
 
@@ -726,7 +765,7 @@ class SimLib:
             fn = getattr(self.dll, prefix + name)  # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
             self.f[name] = fn
-        # the eleven extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
+        # the twelve extensions: (group, the attribute that says whether the library exports it, symbol -> (restype, argtypes)); a group is
         # bound whole or not at all
         count = (C.c_int, [H, C.POINTER(u32), C.POINTER(u32)])
         read = (C.c_int, [H, u32, u32, vp, C.c_size_t, C.POINTER(u32)])
@@ -833,10 +872,20 @@ class SimLib:
                 "catalog_now": (C.c_int, [H, u32, vp, vp, C.c_size_t, C.POINTER(u32)]),
                 "catalog_version": (u32, []),
             }),
+            ("gazette", "has_gazette", {
+                "gazette_start": (C.c_int, [H, u32, u32, u32, u32]),
+                "gazette_count": count,
+                "gazette_read": read,
+                "gazette_nodes": (C.c_int, [H, u32, u32, vp]),
+                "gazette_subjects": (C.c_int, [H, u32, u32, vp]),
+                "gazette_top": (C.c_int, [H, u32, u32, u32, vp]),
+                "gazette_stop": stop,
+                "gazette_version": (u32, []),
+            }),
         ]
         assert [tuple(sigs) for _, _, sigs in ext] == [TRACK_SYMBOLS, SERIES_SYMBOLS, CENSUS_SYMBOLS, ROLL_SYMBOLS, LEDGER_SYMBOLS,
                                                            DETECT_SYMBOLS, SPREAD_SYMBOLS, TRAFFIC_SYMBOLS, TREE_SYMBOLS, QBOARD_SYMBOLS,
-                                                           CATALOG_SYMBOLS]
+                                                           CATALOG_SYMBOLS, GAZETTE_SYMBOLS]
         self.ext = {}   # group -> exported
         for group, attr, sigs in ext:
             self.ext[group] = all(hasattr(self.dll, prefix + name) for name in sigs)
@@ -908,6 +957,10 @@ class SimLib:
     def catalog_version(self):
         """SIM_CATALOG_VERSION of include/serf_sim_catalog.h, or None when the library has no rumour catalogue."""
         return self.f["catalog_version"]() if self.has_catalog else None
+
+    def gazette_version(self):
+        """SIM_GAZETTE_VERSION of include/serf_sim_gazette.h, or None when the library has no member gazette."""
+        return self.f["gazette_version"]() if self.has_gazette else None
 
 
 class Sim:
@@ -1600,6 +1653,56 @@ class Sim:
         self._ck(self._ext_fn("catalog", "now")(self.h, kinds_mask, hdr.ctypes.data, out.ctypes.data, CATALOG_LIVE * 8, C.byref(got)),
                  "sim_catalog_now")
         return hdr[0], out[:got.value]
+
+    # ---- member gazette (include/serf_sim_gazette.h) ----
+    def gazette_start(self, first_tick=0, period=1, capacity=1 << 12, flap_window=60):
+        """Starts a gazette: the shadow of every view entry's bits is taken now, and behind every tick t >= first_tick with
+        (t - first_tick) % period == 0, until `capacity` samples are held (a first_tick that has passed means "now"), every
+        running node's entries are diffed against it: joins, leaves, failures, reaps, flaps (a join out of Failed less than
+        flap_window ticks after the failure), suspicions raised and cleared, per node and per subject."""
+        self._ck(self._ext_fn("gazette", "start")(self.h, first_tick, period, capacity, flap_window), "sim_gazette_start")
+
+    def gazette_count(self):
+        """(samples taken, samples dropped because the buffer was full); waits for nothing."""
+        return self._sample_count("gazette")
+
+    def gazette_read(self, first=0, n=None):
+        """Samples first .. first + n - 1 (n = None: all that were taken from `first` on) as a numpy array of
+        GAZETTE_SAMPLE_DTYPE; waits for the handle's stream."""
+        fn = self._ext_fn("gazette", "read")
+        if n is None:
+            n = max(0, self._sample_count("gazette")[0] - first)
+        out = np.zeros(max(1, n), GAZETTE_SAMPLE_DTYPE)
+        got = C.c_uint32()
+        self._ck(fn(self.h, first, n, out.ctypes.data, max(1, n) * GAZETTE_WORDS, C.byref(got)), "sim_gazette_read")
+        return out[:got.value]
+
+    def _gazette_rows(self, which, first, n):
+        if n is None:
+            n = max(0, self.cfg.n_nodes - first)
+        out = np.zeros((max(1, n), GAZETTE_COLS), np.uint32)
+        self._ck(self._ext_fn("gazette", which)(self.h, first, n, out.ctypes.data), f"sim_gazette_{which}")
+        return out[:n]
+
+    def gazette_nodes(self, first=0, n=None):
+        """Rows first .. first + n - 1 (n = None: up to the last node) of the node map as uint32 [n][8] (GAZETTE_COLUMNS): what
+        each node's application saw; waits for the handle's stream."""
+        return self._gazette_rows("nodes", first, n)
+
+    def gazette_subjects(self, first=0, n=None):
+        """The same slice of the subject map: how many observers announced each subject joined, failed, ..."""
+        return self._gazette_rows("subjects", first, n)
+
+    def gazette_top(self, which=GAZETTE_MAP_NODES, column=GAZETTE_FAILED, k=10):
+        """ALL rows of a map ranked on the device by a column descending, ties by ascending id: the first k as a numpy array
+        of GAZETTE_RANK_DTYPE (places beyond n_nodes: id 0xFFFFFFFF and zeros); waits for the handle's stream."""
+        top = np.zeros(max(1, k), GAZETTE_RANK_DTYPE)
+        self._ck(self._ext_fn("gazette", "top")(self.h, which, column, k, top.ctypes.data), "sim_gazette_top")
+        return top[:k]
+
+    def gazette_stop(self):
+        """Ends the gazette and frees the samples, the maps and the shadow."""
+        self._sample_stop("gazette")
 
     def snapshot(self):
         """Canonical image of the whole simulated cluster (bytes); restores into any implementation of the ABI."""

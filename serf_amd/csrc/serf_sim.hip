@@ -90,3 +90,4 @@ extern "C" {
 #include "serf_sim_tree.inc"  // include/serf_sim_tree.h: likewise
 #include "serf_sim_qboard.inc"  // include/serf_sim_qboard.h: likewise
 #include "serf_sim_catalog.inc"  // include/serf_sim_catalog.h: likewise
+#include "serf_sim_gazette.inc"  // include/serf_sim_gazette.h: likewise

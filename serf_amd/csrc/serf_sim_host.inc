@@ -36,9 +36,11 @@ struct SplitArr {
 enum { SP_VIEW = 0, SP_EV = 1, SP_Q = 2, SP_N = 3 };  // (the order of SIM_ARR_VIEW .. SIM_ARR_QRING and of the image's sections)
 enum { OB_SERIES = 0, OB_CENSUS = 1, OB_ROLL = 2, OB_LEDGER = 3, OB_DETECT = 4, OB_SPREAD = 5, OB_TRAFFIC = 6, OB_TREE = 7, OB_N = 8 };  // the periodic observers, in the order their samples follow a tick on the stream
 // ... and behind them the query board (serf_sim_qboard.inc): the ninth entry of the table.  It stands in a line of its own because
-// tests/test_tree.py pins the line above as it is; behind the board the rumour catalogue (serf_sim_catalog.inc); OB_ALL is what the table holds
-enum { OB_QBOARD = OB_N, OB_CATALOG = OB_N + 1, OB_ALL = OB_N + 2 };
-static_assert(OB_QBOARD == 8 && OB_CATALOG == 9 && OB_ALL == 10, "the observers' table: eight of rumours and members, the query board, the rumour catalogue");
+// tests/test_tree.py pins the line above as it is; behind the board the rumour catalogue (serf_sim_catalog.inc), behind that the member
+// gazette (serf_sim_gazette.inc); OB_ALL is what the table holds
+enum { OB_QBOARD = OB_N, OB_CATALOG = OB_N + 1, OB_GAZETTE = OB_N + 2, OB_ALL = OB_N + 3 };
+static_assert(OB_QBOARD == 8 && OB_CATALOG == 9 && OB_GAZETTE == 10 && OB_ALL == 11,
+              "the observers' table: eight of rumours and members, the query board, the rumour catalogue, the member gazette");
 // Function-local device scratch: freed when it goes out of scope — behind whatever stream synchronisation stands before that.
 template <typename T>
 struct DevScratch {
@@ -356,7 +358,7 @@ static int rings_need(sim_handle* h) {
 #define EV_CAP (1u << 20)
 
 // ---- what the observers share on the host (the device part: serf_sim_observe.inc; it stands here because it needs the handle) ----
-// trackers, series, census, roll, ledger, detection log, spread map, traffic meter, rumour tree, query board and rumour catalogue watch a handle that holds every node, between ticks
+// trackers, series, census, roll, ledger, detection log, spread map, traffic meter, rumour tree, query board, rumour catalogue and member gazette watch a handle that holds every node, between ticks
 static int observer_usable(const sim_handle* h) {
   if (!h) return SIM_EINVAL;
   if (h->d.sharded || h->in_tick) return SIM_ESTATE;

@@ -29,6 +29,7 @@
 #include "../../include/serf_sim_tree.h"
 #include "../../include/serf_sim_qboard.h"
 #include "../../include/serf_sim_catalog.h"
+#include "../../include/serf_sim_gazette.h"
 #include "../../include/serf_sim_detect.h"
 #include "wire.hpp"
 
@@ -617,6 +618,29 @@ class Cluster {
     s.live.resize(got);
     return s;
   }
+  // member gazette (include/serf_sim_gazette.h): every node's member events — Join / Leave / Failed / Reap, flaps, suspicions raised and
+  // cleared — counted per node and per subject by diffing every view entry's bits against the previous sample's, behind every period-th
+  // tick: a sample of 64 words, a node map and a subject map of eight columns a row (SIM_GAZETTE_JOIN ..), read whole, in slices or ranked.
+  struct GazetteSample { uint64_t w[SIM_GAZETTE_WORDS]; };  // the words of the header's table
+  void gazette_start(uint32_t first_tick = 0, uint32_t period = 1, uint32_t capacity = 1u << 12, uint32_t flap_window = 60) {
+    check(sim_gazette_start(h_, first_tick, period, capacity, flap_window), "sim_gazette_start");
+  }
+  std::pair<uint32_t, uint32_t> gazette_count() const { return sample_count(sim_gazette_count, "sim_gazette_count"); }
+  std::vector<GazetteSample> gazette_read(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) {  // (default: all from `first` on)
+    return sample_read<GazetteSample>(sim_gazette_count, sim_gazette_read, "sim_gazette", first, n, SIM_GAZETTE_WORDS,
+                                      [](const uint64_t* w, GazetteSample& s) { std::memcpy(s.w, w, sizeof s.w); });
+  }
+  // rows first .. first + n - 1 of the node map / the subject map (default: up to the last node)
+  std::vector<sim_gazette_row> gazette_nodes(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) { return gazette_rows(sim_gazette_nodes, "sim_gazette_nodes", first, n); }
+  std::vector<sim_gazette_row> gazette_subjects(uint32_t first = 0, uint32_t n = 0xFFFFFFFFu) { return gazette_rows(sim_gazette_subjects, "sim_gazette_subjects", first, n); }
+  // ALL rows of a map ranked by a column, descending, ties in ascending id: the first k
+  std::vector<sim_gazette_rank> gazette_top(uint32_t map = SIM_GAZETTE_MAP_NODES, uint32_t column = SIM_GAZETTE_FAILED, uint32_t k = 10) {
+    std::vector<sim_gazette_rank> out(k ? k : 1);
+    check(sim_gazette_top(h_, map, column, k, out.data()), "sim_gazette_top");
+    out.resize(k);
+    return out;
+  }
+  void gazette_stop() { check(sim_gazette_stop(h_), "sim_gazette_stop"); }
   // checkpoint / resume (canonical image; snapshot.rs:117-126,228-347 is the per-node analogue)
   std::vector<uint8_t> snapshot() {
     size_t n = 0;
@@ -647,6 +671,14 @@ class Cluster {
   static_assert(sizeof(LedgerSample::Entry) == 8 * SIM_LEDGER_ENTRY_WORDS, "an entry's record is eight words");
   static_assert(sizeof(TrafficSample) == 8 * SIM_TRAFFIC_WORDS && sizeof(TrafficSummary) == 8 * SIM_TRAFFIC_SUMMARY_WORDS,
                 "a traffic sample is sixty-four words, a column's summary forty");
+  std::vector<sim_gazette_row> gazette_rows(int (*rows)(sim_handle*, uint32_t, uint32_t, sim_gazette_row*), const char* what, uint32_t first, uint32_t n) {
+    if (n == 0xFFFFFFFFu) n = n_ > first ? n_ - first : 0;
+    std::vector<sim_gazette_row> out(n ? n : 1);
+    check(rows(h_, first, n, out.data()), what);
+    out.resize(n);
+    return out;
+  }
+  static_assert(sizeof(GazetteSample) == 8 * SIM_GAZETTE_WORDS, "a gazette sample is sixty-four words");
   // what the periodic observers share: the count, and "read n samples of `stride` words and unpack each"
   std::pair<uint32_t, uint32_t> sample_count(int (*count)(const sim_handle*, uint32_t*, uint32_t*), const char* what) const {
     uint32_t t = 0, d = 0;

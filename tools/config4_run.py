@@ -288,6 +288,26 @@ def detect_json(args, sim):
             "last_header": None if hdr is None else {name: (hdr[name].tolist() if hdr[name].ndim else int(hdr[name])) for name in hdr.dtype.names}}
 
 
+def gazette_json(args, sim):
+    """The run's member gazette: the per-tick event rates and the flap count (_ffi.gazette_rates), the ten nodes that saw the most
+    `failed` events and the ten subjects most often announced failed."""
+    import numpy as np
+    from serf_amd import _ffi
+    taken, dropped = sim.gazette_count()
+    s, nodes = sim.gazette_read(), sim.gazette_nodes()
+    rates = _ffi.gazette_rates(s, nodes)
+    top = lambda which: [{"id": int(r["id"]), **{name: int(r["row"][k]) for k, name in enumerate(_ffi.GAZETTE_COLUMNS)}}
+                         for r in sim.gazette_top(which, _ffi.GAZETTE_FAILED, 10)]
+    out = {"period": args.gazette, "samples": taken, "dropped": dropped,
+           "what": "include/serf_sim_gazette.h: the member events every running node's application was handed, by view diffs behind "
+                   "the sampled ticks; per_tick: events per tick over the sampled span; per_node: events of columns 0-3 a node saw",
+           "totals": rates["totals"], "per_tick": rates["per_tick"], "flaps": rates["totals"]["flap"], "per_node": rates["per_node"],
+           "dead_time_bins": s["dead_time"].astype(np.int64).sum(axis=0).tolist() if len(s) else [],
+           "nodes_most_failed": top(_ffi.GAZETTE_MAP_NODES), "subjects_most_failed": top(_ffi.GAZETTE_MAP_SUBJECTS)}
+    sim.gazette_stop()
+    return out
+
+
 def catalog_json(args, sim):
     """The run's rumour catalogue: what the registry holds by kind (_ffi.catalog_summary), the identities nobody named — every
     record that is not one of the tool's own user events — and the live curve."""
@@ -444,6 +464,7 @@ def run_tracker(args, sim, lib):
     detect = detect_json(args, sim) if args.detect else None
     traffic = traffic_json(args, sim) if args.traffic else None
     catalog = catalog_json(args, sim) if args.catalog else None
+    gazette = gazette_json(args, sim) if args.gazette else None
 
     def rounds(name):
         return [r[name] - t for t, r in done_ev if r[name] != NEVER]
@@ -485,6 +506,8 @@ def run_tracker(args, sim, lib):
         out["traffic"] = traffic
     if catalog:
         out["catalog"] = catalog
+    if gazette:
+        out["gazette"] = gazette
     json.dump(out, open(args.out, "w"), indent=None if series or census or roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "sim_step_calls", "crashes", "events", "false_positives", "model_bound_drops", "ops_dropped_no_slot", "wall_s")}), "->", args.out)
     print(json.dumps({"rounds_to_99": out["rounds_to"]["99"], "detection": out["detection"]}))
@@ -529,6 +552,7 @@ def main():
     ap.add_argument("--detect", type=int, default=0, metavar="PERIOD", help="judge every subject with a view slot on the device behind every PERIOD-th tick (include/serf_sim_detect.h): the episodes of every crash and every accusation of the run, their summary into the JSON")
     ap.add_argument("--tree", action="store_true", help="--tracker: follow the first 64 user events with rumour trees, latched behind every tick (include/serf_sim_tree.h), and put their hop histograms, depths, orphans and the ten nodes with the most children into the JSON")
     ap.add_argument("--traffic", type=int, default=0, metavar="PERIOD", help="meter the gossip packets per sender and per target on the device behind every PERIOD-th tick (include/serf_sim_traffic.h): per-node byte percentiles and the ten hottest receivers into the JSON")
+    ap.add_argument("--gazette", type=int, default=0, metavar="PERIOD", help="count every node's member events on the device behind every PERIOD-th tick (include/serf_sim_gazette.h): the per-tick rates, the flaps, the ten nodes that saw the most failed events and the ten subjects most often announced failed into the JSON")
     ap.add_argument("--catalog", type=int, default=0, metavar="PERIOD", help="find the live record identities on the device behind every PERIOD-th tick (include/serf_sim_catalog.h): the registry by kind, the identities nobody named and the live curve into the JSON")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -571,6 +595,8 @@ def main():
         sim.traffic_start(0, args.traffic, min(_ffi.TRAFFIC_MAX_SAMPLES, 1 << 16))
     if args.catalog:
         sim.catalog_start(_ffi.CATALOG_KINDS, _ffi.CATALOG_MAX, 0, args.catalog, min(_ffi.CATALOG_MAX_SAMPLES, 1 << 16))
+    if args.gazette:
+        sim.gazette_start(0, args.gazette, min(_ffi.GAZETTE_MAX_SAMPLES, 1 << 16), 60)
     if args.tracker:
         return run_tracker(args, sim, lib)
     rng = np.random.default_rng(5)
@@ -626,7 +652,7 @@ def main():
     out = {
         "what": "BASELINE configs[4] on one GPU: churn + packet loss with the SWIM layer on; rounds until >= 99 % of the running nodes have "
                 "applied a user event",
-        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect", "spread", "traffic", "tree", "catalog")},
+        "config": {k: v for k, v in vars(args).items() if k not in ("out", "lib", "tracker", "ticks", "crash_prob", "crash_cap", "burst", "fp_sample", "series", "census", "roll", "ledger", "detect", "spread", "traffic", "tree", "catalog", "gazette")},
         "backend": lib.backend_name(),
         "ticks": int(sim.tick), "churn_events": int(n_churn), "churn_frac_of_nodes": n_churn / n, "rumors": int(len(r)),
         "rounds_to_99": {"median": float(np.median(r)), "p90": float(np.percentile(r, 90)), "p99": float(np.percentile(r, 99)),
@@ -661,6 +687,8 @@ def main():
         out["traffic"] = traffic_json(args, sim)
     if args.catalog:
         out["catalog"] = catalog_json(args, sim)
+    if args.gazette:
+        out["gazette"] = gazette_json(args, sim)
     json.dump(out, open(args.out, "w"), indent=None if args.series or args.census or args.roll else 1)
     print(json.dumps({k: out[k] for k in ("ticks", "churn_events", "rounds_to_99", "model_bound_drops", "ops_dropped_no_slot", "failure_detector", "wall_s")}), "->", args.out)
 
